@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: VAE_HMM train-step sequences/sec on MI355X.
 
-    python bench.py [--gpus N --steps K --warmup W --scaling strong|weak]
+    python bench.py [--gpus N --steps K --warmup W --scaling strong|weak] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -21,7 +21,13 @@ Multi-GPU: one process per GPU over RCCL.  Under torchrun the world comes from
 its env (it must equal --gpus); a bare `python bench.py --gpus N` spawns the N
 rank processes itself (fresh interpreters; the parent never touches the GPU).
 
-Also reported (rank 0):
+A plain run sets up, warms up, times the K steps and prints the result line.
+--dump-outputs DIR then writes what the last timed step left with its caller
+(loss, updated parameters, gradient, Adam moments: flat float32 vectors in the
+C ABI's parameter order) as DIR/<name>.npy; inputs and weights are seeded, so
+two builds run with the same arguments can be compared array for array.
+
+Reported only with --full (rank 0), each in runs of its own after the timed steps:
   roofline      dominant kernel of the step, timed live with HIP events on the
                 launch stream over instrumented steps; achieved = algorithmic
                 FLOPs (or bytes) per launch / average launch duration
@@ -79,6 +85,12 @@ def parse():
                          "(its 5 launches: 0.0945 vs 0.0994 ms as a graph at B = 128), one HIP graph for the "
                          "data-parallel form (the all-reduce captured: 0.1005 vs 0.1069 ms eager)")
     ap.add_argument("--no-graph", action="store_true", help="same as --launch eager")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (loss, parameters, gradient, "
+                         "Adam moments) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the per-stage rooflines, the VQ / HMM kernel legs and the "
+                         "CPU baseline (trimmed by --profile-steps 0, --no-hmm, --no-cpu-baseline)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--profile-steps", type=int, default=5)
@@ -365,6 +377,26 @@ def cpu_baseline(cfg, B, seconds):
             f"the host does not scale this workload: {best} threads give {sweep[best] / sweep[1]:.2f}x one thread"}
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, st):
+    """What the last timed step left with its caller, as <path>/<name>.npy (float32): the loss it returned,
+    the parameters it updated in place, the gradient publish_grads() hands out and Adam's two moments, each
+    the flat vector in the C ABI's parameter order.  Arrays that would take the dump past 64 MB in all are
+    cut to a fixed, seeded sample of their elements (kept in index order)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    outs = {"loss": st.loss.reshape(1), "params": st.flat, "grad": st.grad, "exp_avg": st.exp_avg,
+            "exp_avg_sq": st.exp_avg_sq}
+    cap = DUMP_MAX_BYTES // (4 * len(outs))  # elements per array
+    for name, t in outs.items():
+        arr = t.detach().to(torch.float32).cpu().numpy().reshape(-1)
+        if arr.size > cap:
+            arr = arr[np.sort(np.random.default_rng(1234).choice(arr.size, cap, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(arr))
+
+
 def spawn_ranks(n):
     """`python bench.py --gpus N` without torchrun: start N fresh rank processes (this
     parent never touches the GPU) on 127.0.0.1; report every rank's exit code or signal
@@ -481,11 +513,13 @@ def main():
     ms_per_step = elapsed / a.steps * 1e3
     value = Bglob * a.steps / elapsed
     st.check_status()  # any device-side error word set during the timed steps raises here
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, st)
 
     roof = None
     kernels = None
     stage_roof = None
-    if rank == 0 and a.profile_steps > 0:
+    if a.full and rank == 0 and a.profile_steps > 0:
         stages = stage_timings(lib, st, x, u, L, B, T, beta, a.profile_steps)
         dom = max(stages, key=lambda s: s["us"])
         dur = dom["us"] * 1e-6
@@ -521,11 +555,11 @@ def main():
                 ach = sd["bytes"] / dur / 1e9
                 stage_roof[sd["name"]] = {"bound": "hbm", "us": round(sd["us"], 2), "achieved": round(ach, 1),
                                           "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBPS, 4)}
-    vq = vq_cfg3(lib) if rank == 0 and world == 1 else None
-    hmm = hmm_kernels(lib) if rank == 0 and world == 1 and not a.no_hmm else {}
+    vq = vq_cfg3(lib) if a.full and rank == 0 and world == 1 else None
+    hmm = hmm_kernels(lib) if a.full and rank == 0 and world == 1 and not a.no_hmm else {}
 
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         cpu = cpu_baseline(cfg, B, a.cpu_seconds)
 
     if rank == 0:
@@ -534,7 +568,7 @@ def main():
             # (BASELINE.json's metric names cfg2; --config cfg3 / cfg4 report the same quantity at those shapes)
             "value": round(value, 1), "unit": "sequences/s", "n_gpus": world, "steps": a.steps,
             "warmup": a.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
-            "scaling": a.scaling, "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "scaling": a.scaling, "full": a.full, "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": f"{a.config}: VAE_HMM train step (compute_loss+backward+Adam)",
                        "global_batch": Bglob, "per_gpu_batch": B, "seq_len": T, "K": K, "input_dim": D,
                        "hidden_dim": H, "hidden_dim2": H2, "u_dim": U, "trans_hidden": TH,
@@ -550,7 +584,7 @@ def main():
             "step_kernels_us": kernels,
             "step_kernels_note": ("HIP-event time of each launch of the step run stage by stage (the forward "
                                   "finalizing its own loss: need_grad=1, one launch the timed step does not "
-                                  "have); each includes ~5 us of event overhead"),
+                                  "have); each includes ~5 us of event overhead") if a.full else None,
             "stage_roofline": stage_roof, "vq_cfg3": vq, **hmm,
         }
         if cpu:
