@@ -128,6 +128,35 @@ int vqhmm_fwdbwd_f32(const float* log_pi, const float* log_A, const float* em, c
                      int64_t B, int64_t T, int64_t K, float* gamma, float* logZ, void* workspace,
                      size_t ws_bytes, void* stream);
 
+/* ------------------------------------- causal filter, pairwise posteriors ----
+ * Same inputs as Viterbi, 1 <= K <= 32 (larger K -> VQHMM_EUNSUPPORTED); hmm_pair.hip.
+ *
+ * vqhmm_filter_f32: filt (B,T,K) fp32 with filt[b,t,j] = p(z_t = j | x_{1:t}) (each row t < length
+ * sums to 1; rows t >= length are 0) and loglik (B) fp32 = log p(x_{1:length}) (NaN if length 0,
+ * as logZ).  The chain runs on linear probabilities normalised at every step; the logs of the step
+ * masses are summed in fp64.  A step whose mass leaves [2^-30, 2^30] is redone as a max-shifted
+ * log-sum-exp step; a sequence whose mass is truly 0 gets loglik = -inf (its filt from that step on
+ * is unspecified) and leaves the other sequences untouched.  No workspace.
+ * Accuracy target vs the fp64 oracle: |filt| abs 1e-5, loglik rel 1e-5.
+ *
+ * vqhmm_fwdbwd_xi_f32: gamma and logZ exactly as vqhmm_fwdbwd_f32 writes them (the same launch:
+ * the same bits), and xi (B,T,K,K) fp32 with xi[b,t,i,j] = p(z_{t-1} = i, z_t = j | x_{1:length})
+ * for 1 <= t < length, 0 at t = 0 and at t >= length (every element of xi is written).  Three
+ * launches: forward-backward, the filter (into the workspace), then
+ *   xi_t(i,j) = gamma_t(j) * filt_{t-1}(i) A_t(i,j) / sum_i' filt_{t-1}(i') A_t(i',j),
+ * whose columns sum to gamma_t(j) by construction; a column whose denominator is 0 (structural
+ * -inf in log_A) is 0, never NaN.  These are the gradients of logZ: d logZ / d log_A = xi,
+ * d logZ / d em = gamma, d logZ / d log_pi = sum_b gamma[b,0].
+ * Workspace: vqhmm_fwdbwd_xi_workspace_size(B, T, K) bytes (0 if K is unsupported).
+ * Accuracy target vs the fp64 oracle: |xi| abs 2e-5.
+ * Neither kernel reads outside [0, B*T*K*K) of log_A or [0, B*T*K) of em / gamma. */
+int vqhmm_filter_f32(const float* log_pi, const float* log_A, const float* em, const int64_t* lengths,
+                     int64_t B, int64_t T, int64_t K, float* filt, float* loglik, void* stream);
+size_t vqhmm_fwdbwd_xi_workspace_size(int64_t B, int64_t T, int64_t K);
+int vqhmm_fwdbwd_xi_f32(const float* log_pi, const float* log_A, const float* em, const int64_t* lengths,
+                        int64_t B, int64_t T, int64_t K, float* gamma, float* xi, float* logZ,
+                        void* workspace, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------- training step ----
  * compute_loss forward + backward of VAE_HMM (VQ_VAE_HMM_fixed.py:106-137,
  * autograd of :156) as one native executor over hand-written kernels.

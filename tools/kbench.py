@@ -1,6 +1,7 @@
 """Kernel micro-benchmarks (HIP events on the launch stream).
 
     python tools/kbench.py vq [--B 2048 --Dv 64 --T 200 --K 32]
+    python tools/kbench.py xi --B 512 --T 512 --K 8     (fwdbwd, filter, xi, combined; alternated)
 """
 import argparse
 import json
@@ -108,6 +109,67 @@ def bench_fwdbwd(a):
                       "frac_hbm": byts / t / HBM_PEAK}))
 
 
+def _pair_legs(a):
+    """The launches behind vqhmm.pairwise_posteriors on one set of tables: name -> callable."""
+    B, T, K = a.B, a.T, a.K
+    log_pi, log_A, em, L = hmm_tables(B, T, K)
+    lib = vqhmm._ext.load()
+    P = vqhmm._ext.ptr
+    st = vqhmm._ext.stream_ptr()
+    gamma = torch.empty(B, T, K, device="cuda")
+    filt = torch.empty(B, T, K, device="cuda")
+    xi = torch.empty(B, T, K, K, device="cuda")
+    logZ = torch.empty(B, device="cuda")
+    nb = lib.vqhmm_fwdbwd_workspace_size(B, T, K)
+    ws = torch.empty(max(nb, 1), dtype=torch.uint8, device="cuda")
+    nbx = lib.vqhmm_fwdbwd_xi_workspace_size(B, T, K)
+    wsx = torch.empty(max(nbx, 1), dtype=torch.uint8, device="cuda")
+    keep = (log_pi, log_A, em, L, gamma, filt, xi, logZ, ws, wsx)
+
+    def fwdbwd():
+        lib.vqhmm_fwdbwd_f32(P(log_pi), P(log_A), P(em), P(L), B, T, K, P(gamma), P(logZ), P(ws), nb, st)
+
+    def filt_fn():
+        lib.vqhmm_filter_f32(P(log_pi), P(log_A), P(em), P(L), B, T, K, P(filt), P(logZ), st)
+
+    def combined():
+        lib.vqhmm_fwdbwd_xi_f32(P(log_pi), P(log_A), P(em), P(L), B, T, K, P(gamma), P(xi), P(logZ), P(wsx), nbx, st)
+
+    return {"fwdbwd": fwdbwd, "filter": filt_fn, "fwdbwd_xi": combined}, keep
+
+
+def bench_filter(a):
+    B, T, K = a.B, a.T, a.K
+    legs, _keep = _pair_legs(a)
+    t = time_fn(legs["filter"], iters=20, warmup=3)
+    byts = B * T * (4 * K * K + 8 * K)
+    print(json.dumps({"kernel": "filter", "B": B, "T": T, "K": K, "us": t * 1e6, "GBps": byts / t / 1e9,
+                      "frac_hbm": byts / t / HBM_PEAK}))
+
+
+def bench_xi(a):
+    """fwdbwd, filter and the combined vqhmm_fwdbwd_xi_f32 in one process, alternated after a
+    warm-up (median of the rounds); the xi launch is the combined call less its two other
+    launches (the three run back to back on one stream).  Algorithmic bytes per position:
+    fwdbwd 4K^2 + 8K, filter 4K^2 + 8K, xi 8K^2 + 8K."""
+    B, T, K = a.B, a.T, a.K
+    legs, _keep = _pair_legs(a)
+    for fn in legs.values():
+        time_fn(fn, iters=3, warmup=2)
+    rounds = {k: [] for k in legs}
+    for _ in range(7):
+        for k, fn in legs.items():
+            rounds[k].append(time_fn(fn, iters=10, warmup=1))
+    t = {k: sorted(v)[len(v) // 2] for k, v in rounds.items()}
+    t["xi"] = t["fwdbwd_xi"] - t["fwdbwd"] - t["filter"]
+    n = B * T
+    byts = {"fwdbwd": n * (4 * K * K + 8 * K), "filter": n * (4 * K * K + 8 * K), "xi": n * (8 * K * K + 8 * K)}
+    byts["fwdbwd_xi"] = sum(byts.values())
+    for k in ("fwdbwd", "filter", "xi", "fwdbwd_xi"):
+        print(json.dumps({"kernel": k, "B": B, "T": T, "K": K, "us": t[k] * 1e6, "GBps": byts[k] / t[k] / 1e9,
+                          "frac_hbm": byts[k] / t[k] / HBM_PEAK, "x_fwdbwd": t[k] / t["fwdbwd"]}))
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("what")
@@ -116,4 +178,5 @@ if __name__ == "__main__":
     ap.add_argument("--T", type=int, default=200)
     ap.add_argument("--K", type=int, default=32)
     a = ap.parse_args()
-    {"vq": bench_vq, "stream": bench_stream, "viterbi": bench_viterbi, "fwdbwd": bench_fwdbwd}[a.what](a)
+    {"vq": bench_vq, "stream": bench_stream, "viterbi": bench_viterbi, "fwdbwd": bench_fwdbwd,
+     "filter": bench_filter, "xi": bench_xi}[a.what](a)

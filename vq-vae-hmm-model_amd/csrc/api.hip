@@ -280,7 +280,7 @@ ConvArgs conv_base(const ElboPlan& p) {
 
 extern "C" {
 
-int32_t vqhmm_abi_version(void) { return 6; }
+int32_t vqhmm_abi_version(void) { return 7; }
 
 int vqhmm_param_layout(const vqhmm_dims_t* d, int64_t off[VQHMM_NPARAMS + 1]) {
   if (!dims_ok(d) || !off) return VQHMM_EINVAL;
@@ -343,6 +343,44 @@ int vqhmm_fwdbwd_f32(const float* log_pi, const float* log_A, const float* em, c
   if (B == 0 || T == 0) return VQHMM_OK;
   if (!ws) return VQHMM_EWORKSPACE;
   return launch_fwdbwd(log_pi, log_A, em, lengths, B, T, K, gamma, logZ, ws, ws_bytes, (hipStream_t)stream);
+}
+
+int vqhmm_filter_f32(const float* log_pi, const float* log_A, const float* em, const int64_t* lengths, int64_t B,
+                     int64_t T, int64_t K, float* filt, float* loglik, void* stream) {
+  if (B < 0 || T < 0 || K < 1 || (B > 0 && (!log_pi || !log_A || !em || !lengths || !filt || !loglik)))
+    return VQHMM_EINVAL;
+  if (!hmm_pair_supported(K)) return VQHMM_EUNSUPPORTED;
+  if (B == 0 || T == 0) return VQHMM_OK;
+  return launch_hmm_filter(log_pi, log_A, em, lengths, B, T, K, filt, loglik, (hipStream_t)stream);
+}
+
+// workspace of vqhmm_fwdbwd_xi_f32: the forward-backward workspace (256-byte rounded), then filt (B,T,K)
+static size_t xi_filt_offset(int64_t B, int64_t T, int64_t K) { return (fwdbwd_ws_bytes(B, T, K) + 255) / 256 * 256; }
+
+size_t vqhmm_fwdbwd_xi_workspace_size(int64_t B, int64_t T, int64_t K) {
+  if (B < 0 || T < 0 || K < 1 || !hmm_pair_supported(K)) return 0;
+  return xi_filt_offset(B, T, K) + hmm_filter_bytes(B, T, K) + sizeof(float) * (size_t)B;
+}
+
+int vqhmm_fwdbwd_xi_f32(const float* log_pi, const float* log_A, const float* em, const int64_t* lengths, int64_t B,
+                        int64_t T, int64_t K, float* gamma, float* xi, float* logZ, void* ws, size_t ws_bytes,
+                        void* stream) {
+  if (B < 0 || T < 0 || K < 1 || (B > 0 && (!log_pi || !log_A || !em || !lengths || !gamma || !xi || !logZ)))
+    return VQHMM_EINVAL;
+  if (!hmm_pair_supported(K)) return VQHMM_EUNSUPPORTED;
+  if (B == 0 || T == 0) return VQHMM_OK;
+  if (!ws || ws_bytes < vqhmm_fwdbwd_xi_workspace_size(B, T, K)) return VQHMM_EWORKSPACE;
+  hipStream_t s = (hipStream_t)stream;
+  // 1. gamma and logZ by the forward-backward launch itself: the same bits as vqhmm_fwdbwd_f32
+  int rc = launch_fwdbwd(log_pi, log_A, em, lengths, B, T, K, gamma, logZ, ws, fwdbwd_ws_bytes(B, T, K), s);
+  if (rc != VQHMM_OK) return rc;
+  // 2. the causal filter into the workspace (its log-likelihood lands behind it, unused here)
+  float* filt = reinterpret_cast<float*>(static_cast<char*>(ws) + xi_filt_offset(B, T, K));
+  float* loglik = filt + (size_t)B * T * K;
+  rc = launch_hmm_filter(log_pi, log_A, em, lengths, B, T, K, filt, loglik, s);
+  if (rc != VQHMM_OK) return rc;
+  // 3. xi from log_A, filt_{t-1} and gamma_t
+  return launch_hmm_xi(log_A, filt, gamma, lengths, B, T, K, xi, s);
 }
 
 int vqhmm_elbo_workspace_size(const vqhmm_dims_t* d, int64_t B, int64_t T, size_t* bytes) {

@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # VQHMM_LIB_PATH: load another build of the same library (kernel A/B experiments only)
 LIB_PATH = os.environ.get("VQHMM_LIB_PATH") or os.path.join(_HERE, "libvqhmm.so")
 NPARAMS = 18
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 EUNSUPPORTED = -4
 _ERRORS = {-1: "invalid argument", -2: "kernel launch failed", -3: "workspace too small",
@@ -46,6 +46,10 @@ _SIGS = {
     "vqhmm_viterbi_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "vqhmm_fwdbwd_workspace_size": (c_sz, [c_i64, c_i64, c_i64]),
     "vqhmm_fwdbwd_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "vqhmm_filter_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp]),
+    "vqhmm_fwdbwd_xi_workspace_size": (c_sz, [c_i64, c_i64, c_i64]),
+    "vqhmm_fwdbwd_xi_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_sz,
+                                           c_vp]),
     "vqhmm_elbo_workspace_size": (ctypes.c_int, [ctypes.POINTER(Dims), c_i64, c_i64, ctypes.POINTER(c_sz)]),
     "vqhmm_elbo_fwd_f32": (ctypes.c_int, [ctypes.POINTER(Dims), ctypes.POINTER(c_vp), c_vp, c_vp, ctypes.c_int,
                                           c_vp, c_vp, c_i64, c_i64, c_f32, ctypes.c_int, c_vp, c_sz, c_vp, c_vp,

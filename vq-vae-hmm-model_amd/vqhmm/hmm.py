@@ -140,8 +140,8 @@ def viterbi(log_pi, log_A, em, lengths=None):
     return path, score
 
 
-def forward_backward(log_pi, log_A, em, lengths=None):
-    """Posterior state marginals gamma (B,T,K) and log-partition logZ (B,)."""
+def _forward_backward_plain(log_pi, log_A, em, lengths=None):
+    """gamma and logZ as plain tensors (vqhmm_fwdbwd_f32, any supported K)."""
     log_pi, log_A, em, lengths, B, T, K = _hmm_inputs(log_pi, log_A, em, lengths)
     gamma = torch.empty((B, T, K), dtype=torch.float32, device=em.device)
     logZ = torch.empty((B,), dtype=torch.float32, device=em.device)
@@ -152,3 +152,91 @@ def forward_backward(log_pi, log_A, em, lengths=None):
                                     _ext.ptr(gamma), _ext.ptr(logZ), _ext.ptr(ws), nb, _ext.stream_ptr(em.device)),
                "forward_backward")
     return gamma, logZ
+
+
+PAIR_MAX_K = 32  # the filter / xi kernels' state limit (hmm_pair.hip)
+
+
+def _fwdbwd_xi(log_pi, log_A, em, lengths, B, T, K):
+    """vqhmm_fwdbwd_xi_f32 on prepared inputs -> (gamma, xi, logZ)."""
+    gamma = torch.empty((B, T, K), dtype=torch.float32, device=em.device)
+    xi = torch.empty((B, T, K, K), dtype=torch.float32, device=em.device)
+    logZ = torch.empty((B,), dtype=torch.float32, device=em.device)
+    lib = _ext.load()
+    nb = lib.vqhmm_fwdbwd_xi_workspace_size(B, T, K)
+    ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=em.device)
+    _ext.check(lib.vqhmm_fwdbwd_xi_f32(_ext.ptr(log_pi), _ext.ptr(log_A), _ext.ptr(em), _ext.ptr(lengths), B, T, K,
+                                       _ext.ptr(gamma), _ext.ptr(xi), _ext.ptr(logZ), _ext.ptr(ws), nb,
+                                       _ext.stream_ptr(em.device)), "pairwise_posteriors")
+    return gamma, xi, logZ
+
+
+class _LogZFn(torch.autograd.Function):
+    """forward_backward with logZ differentiable: the forward runs vqhmm_fwdbwd_xi_f32 (gamma and logZ
+    by the same launch as the plain path, so the same bits) and keeps gamma and xi, which ARE the
+    gradients: d logZ / d log_A = xi, d logZ / d em = gamma, d logZ / d log_pi = sum_b gamma[b, 0]."""
+
+    @staticmethod
+    def forward(ctx, log_pi, log_A, em, lengths):
+        B, T, K = em.shape
+        gamma, xi, logZ = _fwdbwd_xi(log_pi, log_A, em, lengths, B, T, K)
+        ctx.save_for_backward(gamma, xi, lengths)
+        ctx.mark_non_differentiable(gamma)
+        return gamma, logZ
+
+    @staticmethod
+    def backward(ctx, g_gamma, g_logZ):
+        gamma, xi, lengths = ctx.saved_tensors
+        # a length-0 sequence has logZ = NaN and no gradient: whatever arrives for it is dropped
+        g = torch.where(lengths > 0, g_logZ, torch.zeros_like(g_logZ))
+        d_pi = d_A = d_em = None
+        if ctx.needs_input_grad[0]:
+            d_pi = (g[:, None] * gamma[:, 0]).sum(0) if gamma.shape[1] else torch.zeros_like(gamma[0, 0])
+        if ctx.needs_input_grad[1]:
+            d_A = g[:, None, None, None] * xi
+        if ctx.needs_input_grad[2]:
+            d_em = g[:, None, None] * gamma
+        return d_pi, d_A, d_em, None
+
+
+def forward_backward(log_pi, log_A, em, lengths=None):
+    """Posterior state marginals gamma (B,T,K) and log-partition logZ (B,).
+
+    When log_pi, log_A or em requires grad, logZ carries a grad_fn whose backward is exact:
+    d logZ / d log_A = xi (the pairwise posteriors), d logZ / d em = gamma, d logZ / d log_pi =
+    sum_b gamma[b, 0] (K <= 32); gamma itself is not differentiable.  Without gradient-requiring
+    inputs this is the plain launch; gamma and logZ are the same bits either way."""
+    if not (torch.is_grad_enabled() and any(t.requires_grad for t in (log_pi, log_A, em))):
+        return _forward_backward_plain(log_pi, log_A, em, lengths)
+    log_pi, log_A, em, lengths, B, T, K = _hmm_inputs(log_pi, log_A, em, lengths)
+    if K > PAIR_MAX_K:
+        raise RuntimeError(f"forward_backward: gradients of logZ need K <= {PAIR_MAX_K} states (got K = {K}); "
+                           "detach the inputs for the posteriors alone")
+    if B * T == 0:
+        return _forward_backward_plain(log_pi, log_A, em, lengths)
+    return _LogZFn.apply(log_pi, log_A, em, lengths)
+
+
+def forward_filter(log_pi, log_A, em, lengths=None):
+    """Causal (filtered) posteriors filt (B,T,K), filt[b,t] = p(z_t | x_{1:t}) (rows sum to 1 inside
+    the length, 0 past it), and loglik (B,) = log p(x_{1:L}) (NaN for length 0).  Unlike gamma,
+    filt[b,t] does not look at steps after t.  1 <= K <= 32."""
+    log_pi, log_A, em, lengths, B, T, K = _hmm_inputs(log_pi, log_A, em, lengths)
+    filt = torch.empty((B, T, K), dtype=torch.float32, device=em.device)
+    loglik = torch.empty((B,), dtype=torch.float32, device=em.device)
+    with torch.no_grad():
+        _ext.check(_ext.load().vqhmm_filter_f32(_ext.ptr(log_pi), _ext.ptr(log_A), _ext.ptr(em), _ext.ptr(lengths), B,
+                                                T, K, _ext.ptr(filt), _ext.ptr(loglik), _ext.stream_ptr(em.device)),
+                   f"forward_filter (K = {K}, limit {PAIR_MAX_K})")
+    return filt, loglik
+
+
+def pairwise_posteriors(log_pi, log_A, em, lengths=None):
+    """gamma (B,T,K), xi (B,T,K,K), logZ (B,): xi[b,t,i,j] = p(z_{t-1} = i, z_t = j | x_{1:L}) for
+    1 <= t < L and 0 elsewhere (the E-step statistics of EM on the transition model: sum_t xi_t);
+    gamma and logZ are forward_backward's, bit for bit.  1 <= K <= 32."""
+    log_pi, log_A, em, lengths, B, T, K = _hmm_inputs(log_pi, log_A, em, lengths)
+    if K > PAIR_MAX_K:
+        raise RuntimeError(f"pairwise_posteriors: K <= {PAIR_MAX_K} states (got K = {K})")
+    with torch.no_grad():
+        return _fwdbwd_xi(log_pi.detach(), log_A.detach(), em.detach(), lengths, B, T, K)

@@ -9,6 +9,8 @@
                             computes q and its first argmax, torch.argmax's rule).
   viterbi_regimes(...)      MAP state path under the Prior's tables with the encoder
                             posterior as emission (log_softmax(logits)).
+  filtered_regimes(...)     causal regime probabilities p(z_t | x_{1:t}) and their argmax under the
+                            same tables and emissions (vqhmm_filter_f32): no look-ahead.
   prior_viterbi(...)        Viterbi over Prior.forward's tables computed on the chip from u
                             (SURVEY §8f-3, vqhmm_prior_viterbi_f32): log_A never touches HBM;
                             bit-identical to viterbi(*model.prior(u), em).
@@ -18,7 +20,7 @@ import ctypes
 import torch
 
 from . import _ext
-from .hmm import viterbi
+from .hmm import forward_filter, regime_argmax, viterbi
 
 
 def _device(model):
@@ -101,6 +103,28 @@ def prior_viterbi(prior, u, em, lengths=None):
         return None
     _ext.check(rc, "prior_viterbi")
     return path, score
+
+
+def filtered_regimes(model, x, u, lengths=None):
+    """Look-ahead-free regimes: (regimes (B, T) int64, probs (B, K, T)).
+
+    probs[b, :, t] = p(z_t | x_{1:t}) under the Prior's tables with the encoder posterior as
+    emission (em = log_softmax(logits), as viterbi_regimes forms it), in hard_regimes' layout;
+    regimes = its first argmax (vqhmm_argmax_f32), -1 past each length.  Unlike the smoothed
+    gamma, probs at t conditions on nothing after t (up to the encoder's own receptive field),
+    so a back-test on it has no look-ahead bias (backtesting.py:154-155)."""
+    with torch.no_grad():
+        em = torch.log_softmax(model.encode(x), dim=1).transpose(1, 2).contiguous()
+        log_pi, log_A = model.prior(u)
+        filt, _ = forward_filter(log_pi, log_A, em, lengths)
+        probs = filt.transpose(1, 2).contiguous()
+        regimes = regime_argmax(probs)
+        if lengths is not None:
+            B, T = regimes.shape
+            L = torch.as_tensor(lengths).to(regimes.device, torch.int64)
+            past = torch.arange(T, device=regimes.device)[None, :] >= L[:, None]
+            regimes = regimes.masked_fill(past, -1)
+    return regimes, probs
 
 
 def viterbi_regimes(model, x, u, lengths=None, fused=True):
