@@ -238,6 +238,19 @@ int vqhmm_debug_prof(int which, uint64_t* out, int64_t n);
 int vqhmm_elbo_num_stages(void);
 int vqhmm_elbo_stage_info(const vqhmm_dims_t* dims, int64_t B, int64_t T, int stage, char* name,
                           size_t name_len, double* flops, double* bytes, int* mfma_bound);
+/* Which kernel family the stage's launch runs for these dims and this (B, T): a short stable string
+ * (host-only, read-only; the launchers take their decision from the same functions).
+ *   convolutions      "conv2", "convbig", "convbig+tail", "conv_mm<BM,BN,KCH>" (the generic implicit GEMM and
+ *                     its tile), "...+tail" (fused 1x1 tail), "...+tail_kernel" (the tail as a second launch,
+ *                     N > 256), "fused_pair", "bwd_pair", "strip_fwd", "strip_bwd", "strip_bwdw";
+ *                     dec_conv1's data gradient adds "+logits_bwd[+logits_dg]" for what rides in its epilogue,
+ *                     and the stages that ride there report its family
+ *   weight gradients  "wgrad2", "wgrad2_group", "strip_bwdw", "wgradbig", "wgrad_generic"
+ *   the ELBO head     "pipe", "coop", "mfma", "scalar", "strip_fwd", or
+ *                     "staged:<l1 kernel>;hid=<conv>;lgA=<conv>;dhid=<conv>;dW1=<wgrad>;dW2=<wgrad>"
+ * "unsupported" where the stage's launch would return VQHMM_EUNSUPPORTED.  The string is truncated to
+ * len - 1 characters. */
+int vqhmm_elbo_stage_family(const vqhmm_dims_t* dims, int64_t B, int64_t T, int stage, char* family, size_t len);
 int vqhmm_elbo_stage_f32(const vqhmm_dims_t* dims, const float* const* params, const float* x,
                          const float* u, int u_layout, const int64_t* lengths, const int64_t* norm,
                          int64_t B, int64_t T, float beta, void* workspace, size_t ws_bytes, float* grad, int stage,

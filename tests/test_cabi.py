@@ -75,6 +75,28 @@ def test_status_word_inside_workspace(dims, B, T):
     assert lib.vqhmm_elbo_status_offset(ctypes.byref(d), 0, T, ctypes.byref(off)) == -1
 
 
+def test_stage_family_query_is_host_only():
+    """vqhmm_elbo_stage_family names the kernel family of every stage without a device (ABI 8): cfg2 runs the
+    strips, a bad stage or a null buffer is an invalid argument, and a short buffer truncates."""
+    from vqhmm import _ext
+    lib = _ext.load()
+    assert lib.vqhmm_abi_version() == _ext.ABI_VERSION == 8
+    d = _ext.Dims(5, 64, 3, 32, 4, 128)
+    buf = ctypes.create_string_buffer(64)
+    n = lib.vqhmm_elbo_num_stages()
+    fams = []
+    for st in range(n):
+        assert lib.vqhmm_elbo_stage_family(ctypes.byref(d), 1024, 200, st, buf, len(buf)) == 0
+        fams.append(buf.value.decode())
+    assert fams[3] == "strip_fwd" and fams[6] == "pipe" and fams[13] == "strip_bwdw" and fams[19] == "strip_bwdw"
+    assert all(fams)
+    assert lib.vqhmm_elbo_stage_family(ctypes.byref(d), 1024, 200, n, buf, len(buf)) == -1
+    assert lib.vqhmm_elbo_stage_family(ctypes.byref(d), 1024, 200, 0, None, 0) == -1
+    short = ctypes.create_string_buffer(4)
+    assert lib.vqhmm_elbo_stage_family(ctypes.byref(d), 1024, 200, 3, short, len(short)) == 0
+    assert short.value == b"str"
+
+
 # the A/B switches the release library may read (common.h VQHMM_ENV): each selects between launch paths the
 # GPU tests prove bit-identical (VQHMM_STRIP_HEAD / VQHMM_HEAD: equal within their stated tolerance)
 RELEASE_SWITCHES = {"VQHMM_CONV_FUSE", "VQHMM_TAIL_FUSED", "VQHMM_STRIP", "VQHMM_STRIP_BWD", "VQHMM_STRIP_WGRAD", "VQHMM_STRIP_HEAD",

@@ -145,11 +145,15 @@ def test_prior_autograd_vs_oracle(B, T, K, lay, with_pi):
     _close(ug.grad, u64.grad, "du")
 
 
-@pytest.mark.parametrize("D,H,K,H2", [(16, 64, 8, 32), (64, 256, 32, 128)])
+@pytest.mark.parametrize("D,H,K,H2", [(16, 64, 8, 32), (64, 256, 32, 128), (5, 128, 3, 64),
+                                       (5, 272, 3, 32)])
 def test_forward_autograd_wide_dims(D, H, K, H2):
     """the module backward at cfg4 dims (D = 16, K = 8) and cfg3 dims (D = 64, H = 256, K = 32),
     where other kernels run than at cfg2 (convbig / wgradbig past 64 channels, the channels-first dgrad
-    outputs): every encoder / decoder gradient, dx and dq against the fp64 oracle, small B and T."""
+    outputs): every encoder / decoder gradient, dx and dq against the fp64 oracle, small B and T.  (5, 128, 3, 64):
+    cfg2 with the hidden sizes doubled, where the generic conv_mm_kernel / wgrad_kernel run (channels-first
+    sources and outputs included); (5, 272, 3, 32): H > 256, to_params as conv_tail_kernel with channels-first
+    outputs."""
     m = _model(D=D, H=H, K=K, H2=H2, seed=5)
     B, T = 4, 40
     g = torch.Generator().manual_seed(D + K)
@@ -174,7 +178,8 @@ def test_forward_autograd_wide_dims(D, H, K, H2):
     _close(xg.grad, x64.grad, "dx")
 
 
-@pytest.mark.parametrize("D,H,K,H2", [(16, 64, 8, 32), (64, 256, 32, 128)])
+@pytest.mark.parametrize("D,H,K,H2", [(16, 64, 8, 32), (64, 256, 32, 128), (5, 128, 3, 64),
+                                       (5, 272, 3, 32)])
 def test_decode_autograd_wide_dims(D, H, K, H2):
     """decode alone at cfg4 / cfg3 dims: the decoder gradients and dq against the fp64 oracle."""
     m = _model(D=D, H=H, K=K, H2=H2, seed=6)

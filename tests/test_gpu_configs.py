@@ -39,7 +39,22 @@ def relu_masks(st, B, T):
     return out
 
 
-def check_step_vs_oracle(dims, B, T, seed, full_frac=0.5, rtol_norm=2e-6, independent=False):
+def poison_workspace(st, B, T):
+    """Fill the step's workspace with quiet-NaN floats (0x7fc00000 in every word) and zero the status word
+    again.  Every field of the workspace (api.hip plan_elbo's carve list) is written by the step before the
+    step reads it: the float buffers and slabs by the launches that produce them; the two integer fields are
+    `cnt`, which the prologue writes (need_grad = 2, no norm) before the head and the tail's loss finalize read
+    it and which no launch reads otherwise, and `sync`, of which no kernel reads or writes anything but the
+    status word, whose bits are only ever set.  So nothing stays unpoisoned but that word."""
+    ws = st.workspace(B, T)
+    ws[: ws.numel() // 4 * 4].view(torch.int32).fill_(0x7FC00000)
+    for word in st._status.values():
+        word.zero_()
+    return ws
+
+
+def check_step_vs_oracle(dims, B, T, seed, full_frac=0.5, rtol_norm=2e-6, independent=False, lengths=None,
+                         poison=False):
     """The training step (loss + 18 grads) at (B, T) vs the oracle:
       loss   within 1e-5 relative of the fp32 CPU oracle (the reference's arithmetic);
       grads  within 2e-6 normwise of the fp64 oracle evaluated on the device forward's own
@@ -58,17 +73,14 @@ def check_step_vs_oracle(dims, B, T, seed, full_frac=0.5, rtol_norm=2e-6, indepe
              bounded like the fp64 masks: each flip sits at a pre-activation within fp32 rounding
              of 0 and moves a gradient by ~1e-5; the cfg4 shard's encoder.conv1 grad measured
              2.7e-5 with such flips).
-    The autograd surface (compute_loss + backward) must give the same bits as TrainState."""
+    The autograd surface (compute_loss + backward) must give the same bits as TrainState.
+      lengths=  the batch's lengths instead of the random draw;
+      poison=True: TrainState's workspace is NaN-filled before its step (poison_workspace), so a kernel that
+             reads a pad column, pad row or slab entry nobody wrote this step shows as a NaN."""
     import vqhmm
+    from width_cases import step_inputs
     D, H, K, H2, U, TH = dims
-    torch.manual_seed(0)
-    m = vqhmm.VAE_HMM(D, H, K, H2, u_dim=U, trans_hidden=TH)
-    sd = {k: v.detach().clone() for k, v in m.state_dict().items()}
-    gen = torch.Generator().manual_seed(seed)
-    x = torch.randn(B, D, T, generator=gen)
-    u = torch.randn(B, U, T, generator=gen)
-    L = torch.randint(20 if T > 20 else 1, T + 1, (B,), generator=gen)
-    L[:int(B * full_frac)] = T
+    m, sd, x, u, L = step_inputs(dims, B, T, seed, full_frac, lengths)
     p32 = {k: v.clone().requires_grad_(True) for k, v in sd.items()}
     ref = RM.elbo(p32, x, u, L, 1.0, K, U)
     ref_loss = ref.item()
@@ -81,8 +93,12 @@ def check_step_vs_oracle(dims, B, T, seed, full_frac=0.5, rtol_norm=2e-6, indepe
     auto = {n: prm.grad.clone() for n, prm in mg.named_parameters()}
     st = vqhmm.TrainState(mg, lr=1e-3)
     xs, us, Ls = st.prepare(x, u, L)
+    if poison:
+        poison_workspace(st, B, T)
     st.forward_backward(xs, us, Ls, 1.0)
     torch.cuda.synchronize()
+    if poison:
+        st.check_status()
     assert abs(st.loss.item() - ref_loss) <= LOSS_RTOL * abs(ref_loss), (st.loss.item(), ref_loss)
     assert st.loss.item() == loss.item()
     masks = relu_masks(st, B, T)

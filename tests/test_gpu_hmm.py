@@ -85,8 +85,8 @@ def test_viterbi_cfg5_long_sequence():
 
 
 # K <= 8 forward-backward has three kernels: the parallel-in-time one (hmm_seg.hip: one wave per 64-step
-# segment; by default for 5 <= K <= 8 and 128 <= T <= 1024, VQHMM_FB_SEG=1 forces it for every K <= 8 and
-# T <= 1024, =0 turns it off), the LDS-resident one (whenever its table fits and one round of workgroups
+# segment; by default for 2 <= K <= 8 and 128 <= T <= 1024, but K = 4 only above T = 256 (fwdbwd_seg_ok);
+# VQHMM_FB_SEG=1 forces it for every K <= 8 and T <= 1024, =0 turns it off), the LDS-resident one (whenever its table fits and one round of workgroups
 # covers the batch) and the streaming one (VQHMM_FB_RES=0, read per call).  The streaming one forms gamma
 # inside its chains where its LDS histories fit (T up to ~1000), else through the workspace and a gamma
 # pass (VQHMM_FB_FUSE=0 forces that form; both switches read per call).  The fused form runs two sequence

@@ -51,10 +51,12 @@ def test_hard_regimes_match_torch_argmax_everywhere(case):
     assert np.array_equal(reg.cpu().numpy()[chk], ref_reg[chk])
 
 
-@pytest.mark.parametrize("K,D,H,H2", [(3, 5, 64, 32), (8, 16, 64, 32), (32, 64, 80, 72)])
+@pytest.mark.parametrize("K,D,H,H2", [(3, 5, 64, 32), (8, 16, 64, 32), (32, 64, 80, 72), (3, 5, 128, 64),
+                                       (3, 5, 64, 272)])
 def test_hard_regimes_exact_ties(K, D, H, H2):
     """to_logits rows made identical in pairs: those logits, hence q, tie exactly; the
-    lowest index must win, as in torch.argmax."""
+    lowest index must win, as in torch.argmax.  (3, 5, 128, 64): the softmax / argmax tail on the generic
+    conv_mm_kernel; (3, 5, 64, 272): as a launch of its own (conv_tail_kernel, H2 > 256)."""
     import vqhmm
     torch.manual_seed(K)
     m = vqhmm.VAE_HMM(D, H, K, H2, u_dim=4, trans_hidden=16)

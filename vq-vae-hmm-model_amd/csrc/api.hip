@@ -5,6 +5,7 @@
 #include "vqhmm.h"
 
 #include <math.h>
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -280,7 +281,7 @@ ConvArgs conv_base(const ElboPlan& p) {
 
 extern "C" {
 
-int32_t vqhmm_abi_version(void) { return 7; }
+int32_t vqhmm_abi_version(void) { return 8; }
 
 int vqhmm_param_layout(const vqhmm_dims_t* d, int64_t off[VQHMM_NPARAMS + 1]) {
   if (!dims_ok(d) || !off) return VQHMM_EINVAL;
@@ -504,15 +505,35 @@ int image_jobs(const ElboPlan& p, const float* const* w, WImgJob* jobs) {
 
 // Staged head: Prior MLP as 1x1 convs over PCL rows, L1/L2 row kernels, then the
 // MLP backward as a dgrad conv + two wgrads (head_staged.hip).
+// Its three convolutions (0 hidden layer, 1 transition logits, 2 the hidden layer's data gradient) ...
+ConvArgs staged_conv(const ElboPlan& p, const float* const* w, int i) {
+  ConvArgs a = conv_base(p);
+  if (i == 0) {
+    a.src = p.up; a.Kc = p.U; a.ks = 1; a.W = w[TN0_W]; a.bias = w[TN0_B]; a.N = p.TH; a.act = 1; a.out = p.hid;
+  } else if (i == 1) {
+    a.src = p.hid; a.Kc = p.TH; a.ks = 1; a.W = w[TN2_W]; a.bias = w[TN2_B]; a.N = p.K * p.K; a.act = 0;
+    a.out = p.lgA;
+  } else {
+    a.src = p.lgA; a.Kc = p.K * p.K; a.ks = 1; a.W = w[TN2_W]; a.w_dgrad = 1; a.N = p.TH; a.act = 2; a.aux = p.hid;
+    a.out = p.dhid;
+  }
+  return a;
+}
+// ... and its two weight gradients (0 transition_net.0, 1 transition_net.2)
+WgradArgs staged_wgrad(const ElboPlan& p, int i) {
+  const float* dys[2] = {p.dhid, p.lgA};
+  const float* xs[2] = {p.up, p.hid};
+  const WLayer& L = p.wl[6 + i];
+  WgradArgs wa{};
+  wa.dy = dys[i]; wa.x = xs[i]; wa.x_cf = 0; wa.R = p.R; wa.T = p.T;
+  wa.N = L.N; wa.C = L.C; wa.ks = L.ks; wa.rows_per_chunk = L.rows; wa.slab = L.slab; wa.bias_slab = L.bslab;
+  return wa;
+}
+
 int run_staged_head(const ElboPlan& p, const StepCtx& c, const float* const* w, hipStream_t s) {
   int rc;
-  ConvArgs a = conv_base(p);
-  a.src = p.up; a.Kc = p.U; a.ks = 1; a.W = w[TN0_W]; a.bias = w[TN0_B]; a.N = p.TH; a.act = 1; a.out = p.hid;
-  if ((rc = launch_conv(a, s))) return rc;
-  a = conv_base(p);
-  a.src = p.hid; a.Kc = p.TH; a.ks = 1; a.W = w[TN2_W]; a.bias = w[TN2_B]; a.N = p.K * p.K; a.act = 0;
-  a.out = p.lgA;
-  if ((rc = launch_conv(a, s))) return rc;
+  if ((rc = launch_conv(staged_conv(p, w, 0), s))) return rc;
+  if ((rc = launch_conv(staged_conv(p, w, 1), s))) return rc;
   StagedHeadArgs h{};
   h.B = p.B; h.T = p.T; h.R = p.R; h.D = p.D; h.K = p.K;
   h.x = p.xp; h.par = p.par; h.logits = p.logits; h.q = p.q; h.lengths = c.lengths;
@@ -521,19 +542,9 @@ int run_staged_head(const ElboPlan& p, const StepCtx& c, const float* const* w, 
   h.dpar = p.dpar; h.dlx = p.dlx; h.dqx = p.dqx; h.part = p.part; h.q0 = p.sq0;
   if ((rc = launch_staged_head(h, p.hgrid, s))) return rc;
   if (!c.need_grad) return VQHMM_OK;
-  a = conv_base(p);
-  a.src = p.lgA; a.Kc = p.K * p.K; a.ks = 1; a.W = w[TN2_W]; a.w_dgrad = 1; a.N = p.TH; a.act = 2; a.aux = p.hid;
-  a.out = p.dhid;
-  if ((rc = launch_conv(a, s))) return rc;
-  const float* dys[2] = {p.dhid, p.lgA};
-  const float* xs[2] = {p.up, p.hid};
-  for (int i = 0; i < 2; ++i) {
-    const WLayer& L = p.wl[6 + i];
-    WgradArgs wa{};
-    wa.dy = dys[i]; wa.x = xs[i]; wa.x_cf = 0; wa.R = p.R; wa.T = p.T;
-    wa.N = L.N; wa.C = L.C; wa.ks = L.ks; wa.rows_per_chunk = L.rows; wa.slab = L.slab; wa.bias_slab = L.bslab;
-    if ((rc = launch_wgrad(wa, s))) return rc;
-  }
+  if ((rc = launch_conv(staged_conv(p, w, 2), s))) return rc;
+  for (int i = 0; i < 2; ++i)
+    if ((rc = launch_wgrad(staged_wgrad(p, i), s))) return rc;
   return VQHMM_OK;
 }
 
@@ -734,6 +745,13 @@ bool tail_fused_on() {
 bool tail_applies_adam(const ElboPlan& p, const StepCtx& c) { return c.adam && p.wgroup && tail_fused_on(); }
 int64_t* adam_step_inc(const ElboPlan& p, const StepCtx& c) { return tail_applies_adam(p, c) ? c.adam->step : nullptr; }
 
+// S_HEAD's launch: the staged head, inside the forward strip, head_coop's pipelined or cooperative kernel, or
+// launch_head (fused_head_kind: the tile-barrier MFMA head or the scalar head)
+enum HeadKind { HK_STAGED, HK_STRIP, HK_PIPE, HK_COOP, HK_FUSED };
+int head_kind(const ElboPlan& p) {
+  return p.staged ? HK_STAGED : p.strip_head ? HK_STRIP : p.pipe_head ? HK_PIPE : p.coop_head ? HK_COOP : HK_FUSED;
+}
+
 HeadArgs head_args(const ElboPlan& p, const StepCtx& c) {
   const float* const* w = c.w;
   HeadArgs h{};
@@ -828,11 +846,12 @@ int run_stage(const ElboPlan& p, const StepCtx& c, int st, hipStream_t s) {
       return launch_conv(a, s);
     }
     case S_HEAD: {
-      if (p.staged) return run_staged_head(p, c, w, s);
-      if (p.strip_head) return VQHMM_OK;  // in S_ENC2's strip launch
+      const int hk = head_kind(p);
+      if (hk == HK_STAGED) return run_staged_head(p, c, w, s);
+      if (hk == HK_STRIP) return VQHMM_OK;  // in S_ENC2's strip launch
       const HeadArgs h = head_args(p, c);
-      if (p.pipe_head) return launch_head_pipe(h, p.hgrid, s);
-      if (p.coop_head) return launch_head_coop(h, p.hgrid, s);
+      if (hk == HK_PIPE) return launch_head_pipe(h, p.hgrid, s);
+      if (hk == HK_COOP) return launch_head_coop(h, p.hgrid, s);
       return launch_head(h, p.hgrid, s);
     }
     case S_FINAL:
@@ -981,6 +1000,7 @@ int vqhmm_elbo_fwd_f32(const vqhmm_dims_t* d, const float* const* w, const float
     if (!w[i]) return VQHMM_EINVAL;
   ElboPlan p = plan_elbo(d, B, T, ws);
   if (ws_bytes < p.bytes) return VQHMM_EWORKSPACE;
+  if (p.staged && !staged_head_supported(p.K)) return VQHMM_EUNSUPPORTED;  // before anything is launched
   StepCtx c{w, x, u, u_layout, lengths, norm, beta, need_grad, loss, loss_accum, nullptr, nullptr, nullptr};
   for (int st = FWD_FIRST; st <= FWD_LAST; ++st)
     if (int rc = run_stage(p, c, st, (hipStream_t)stream)) return rc;
@@ -1177,6 +1197,101 @@ int vqhmm_elbo_stage_info(const vqhmm_dims_t* d, int64_t B, int64_t T, int stage
   if (flops) *flops = f;
   if (bytes) *bytes = b;
   if (mfma_bound) *mfma_bound = m;
+  return VQHMM_OK;
+}
+
+// Which kernel family a stage's launch runs: the same predicates, in the same order, as run_stage, on a plan
+// with (never dereferenced) non-null workspace and parameter addresses, as a real step has them.
+int vqhmm_elbo_stage_family(const vqhmm_dims_t* d, int64_t B, int64_t T, int stage, char* out, size_t len) {
+  if (!dims_ok(d) || stage < 0 || stage >= S_COUNT || B <= 0 || T <= 0 || !out || len == 0) return VQHMM_EINVAL;
+  const ElboPlan p = plan_elbo(d, B, T, nullptr);
+  const float* w[VQHMM_NPARAMS];
+  for (int i = 0; i < VQHMM_NPARAMS; ++i) w[i] = reinterpret_cast<const float*>(4096);
+  const char* bstrip = p.wfold ? "strip_bwdw" : "strip_bwd";
+  char buf[256];
+  buf[0] = 0;
+  const char* nm = buf;
+  auto conv = [&](const ConvArgs& a) { conv_family(a, buf, sizeof buf); };
+  auto dec1_dg = [&]() {  // S_DEC1_DG's launch, which S_LOGIT_BWD / S_LOGIT_DG may ride in
+    if (strip_bwd_on(p)) { nm = bstrip; return; }
+    if (bwd_pair_fused(p, w, nullptr)) { nm = "bwd_pair"; return; }
+    const ConvArgs a = dec1_dg_args(p, w, nullptr);
+    conv(a);
+    if (a.act >= 3) strncat(buf, "+logits_bwd", sizeof buf - strlen(buf) - 1);
+    if (a.lb_dh) strncat(buf, "+logits_dg", sizeof buf - strlen(buf) - 1);
+  };
+  switch (stage) {
+    case S_TOPCL: nm = "prologue"; break;
+    case S_COMPOSE: nm = "(prologue)"; break;
+    case S_ENC1: case S_DEC1:
+      if (strip_fwd_on(p)) nm = "strip_fwd";
+      else if (front_fused(p, w, stage + 1)) nm = "fused_pair";
+      else conv(conv_of(p, w, stage));
+      break;
+    case S_ENC2: case S_DEC2:
+      if (strip_fwd_on(p)) nm = "strip_fwd";
+      else if (p.strip_head) nm = "unsupported";
+      else if (front_fused(p, w, stage)) nm = "fused_pair";
+      else conv(conv_of(p, w, stage));
+      break;
+    case S_PAR_DG:
+      if (strip_bwd_on(p)) nm = bstrip;
+      else if (front_fused(p, w, S_DEC2_DG)) nm = "fused_pair";
+      else conv(conv_of(p, w, stage));
+      break;
+    case S_DEC2_DG:
+      if (strip_bwd_on(p)) nm = bstrip;
+      else if (front_fused(p, w, stage)) nm = "fused_pair";
+      else conv(conv_of(p, w, stage));
+      break;
+    case S_DEC1_DG: dec1_dg(); break;
+    case S_LOGIT_BWD:
+      if (strip_bwd_on(p) || logits_bwd_fused(p)) dec1_dg();
+      else nm = "logits_bwd";
+      break;
+    case S_LOGIT_DG:
+      if (strip_bwd_on(p) || logits_dg_fused(p)) dec1_dg();
+      else conv(conv_of(p, w, stage));
+      break;
+    case S_ENC2_DG:
+      if (strip_bwd_on(p)) nm = bstrip;
+      else if (bwd_pair_fused(p, w, nullptr)) nm = "bwd_pair";
+      else conv(conv_of(p, w, stage));
+      break;
+    case S_HEAD: {
+      const int hk = head_kind(p);
+      HeadArgs h{};
+      h.K = p.K; h.U = p.U; h.TH = p.TH; h.D = p.D; h.R = p.R;
+      if (hk == HK_STAGED) {
+        char c0[48], c1[48], c2[48];
+        conv_family(staged_conv(p, w, 0), c0, sizeof c0);
+        conv_family(staged_conv(p, w, 1), c1, sizeof c1);
+        conv_family(staged_conv(p, w, 2), c2, sizeof c2);
+        snprintf(buf, sizeof buf, "staged:%s;hid=%s;lgA=%s;dhid=%s;dW1=%s;dW2=%s", staged_l1_name(p.K), c0, c1, c2,
+                 wgrad_family(staged_wgrad(p, 0)), wgrad_family(staged_wgrad(p, 1)));
+      } else if (hk == HK_STRIP) nm = "strip_fwd";
+      else if (hk == HK_PIPE) nm = "pipe";
+      else if (hk == HK_COOP) nm = "coop";
+      else {
+        const int fk = fused_head_kind(h);
+        nm = fk == HEAD_MFMA ? "mfma" : fk == HEAD_SCALAR ? "scalar" : "unsupported";
+      }
+      break;
+    }
+    case S_FINAL: nm = "finalize_loss"; break;
+    case S_W_PAR: case S_W_DEC2: case S_W_DEC1: case S_W_LOGIT: case S_W_ENC2: case S_W_ENC1: {
+      if (p.wfold) { nm = "strip_bwdw"; break; }
+      if (p.wgroup) { nm = "wgrad2_group"; break; }
+      WgradArgs wa[6];
+      wgrad_jobs(p, w, wa);
+      nm = wgrad_family(wa[stage - S_W_PAR]);
+      break;
+    }
+    case S_REDUCE: nm = p.wgroup && tail_fused_on() ? "tail" : "grad_tail"; break;
+    case S_COMPOSE_BWD: nm = p.wgroup ? (tail_fused_on() ? "tail" : "adam") : "compose_bwd"; break;
+    case S_LOGPRIOR: nm = p.wgroup && tail_fused_on() ? "tail" : "grad_tail"; break;
+  }
+  snprintf(out, len, "%s", nm);
   return VQHMM_OK;
 }
 

@@ -21,6 +21,10 @@
 // one float4 of A and one of B from LDS and issues 4 MFMAs per 16x16 block;
 // the k index inside a slice is permuted (lane group g, element e <-> channel
 // 4g+e) identically for A and B, so the sum is unchanged.
+#include <stdio.h>
+
+#include <algorithm>
+
 #include "kernels.h"
 
 namespace vqhmm {
@@ -29,6 +33,69 @@ namespace vqhmm {
 __device__ __forceinline__ float weff(const ConvArgs& a, int n, int c, int tap) {
   if (!a.w_dgrad) return a.W[((int64_t)n * a.Kc + c) * a.ks + tap];
   return a.W[((int64_t)c * a.N + n) * a.ks + (a.ks - 1 - tap)];
+}
+
+// The 1x1 tail of BM rows from m0: z = tW @ y + tb (and softmax over C2), thread per row.  Y[row * ldy + n] are the
+// rows' activated outputs (conv_mm_kernel's LDS tile, or the stored PCL activation for conv_tail_kernel; rows
+// that are not valid positions are never read), Zs [BM][C2 + 1] floats of LDS.
+__device__ __forceinline__ void conv_tail_rows(const ConvArgs& a, const float* Y, int ldy, int64_t m0, int BM,
+                                               float* Zs) {
+  const int tid = threadIdx.x;
+  const int LDZ = a.C2 + 1;
+  for (int row = tid; row < BM; row += 256) {
+    const int64_t r = m0 + row;
+    int64_t b;
+    int t;
+    const bool valid = row_bt(r, a.R, a.T, b, t);
+    float mx = -__builtin_inff();
+    for (int c2 = 0; c2 < a.C2; ++c2) {
+      float z = 0.f;
+      if (valid) {
+        z = a.tb ? a.tb[c2] : 0.f;
+        const float* w = a.tW + (int64_t)c2 * a.N;
+        for (int n = 0; n < a.N; ++n) z = fmaf(w[n], Y[row * ldy + n], z);
+      }
+      Zs[row * LDZ + c2] = z;
+      mx = fmaxf(mx, z);
+      if (a.t_out && r < a.R) a.t_out[r * ld4(a.C2) + c2] = z;
+    }
+    for (int c2 = a.C2; c2 < ld4(a.C2); ++c2) {
+      if (a.t_out && r < a.R) a.t_out[r * ld4(a.C2) + c2] = 0.f;
+      if (a.q_out && r < a.R) a.q_out[r * ld4(a.C2) + c2] = 0.f;
+    }
+    if (a.q_out || a.q_cf || a.reg_out) {
+      float s = 0.f;
+      for (int c2 = 0; c2 < a.C2; ++c2) s += __expf(Zs[row * LDZ + c2] - mx);
+      float bq = -__builtin_inff();
+      int bi = 0x7fffffff;
+      for (int c2 = 0; c2 < a.C2; ++c2) {
+        const float q = valid ? __expf(Zs[row * LDZ + c2] - mx) / s : 0.f;
+        if (a.q_out && r < a.R) a.q_out[r * ld4(a.C2) + c2] = q;
+        if (a.q_cf) Zs[row * LDZ + c2] = q;
+        if (argmax_beats(q, c2, bq, bi)) { bq = q; bi = c2; }
+      }
+      if (a.reg_out && valid) a.reg_out[b * a.T + t] = bi;  // hard regime (backtesting.py:154-155)
+    }
+  }
+  if (a.t_cf0 || a.q_cf) {
+    __syncthreads();
+    for (int i = tid; i < BM * a.C2; i += 256) {
+      const int row = i % BM, c2 = i / BM;
+      const int64_t r = m0 + row;
+      int64_t b;
+      int t;
+      if (!row_bt(r, a.R, a.T, b, t)) continue;
+      const float v = Zs[row * LDZ + c2];
+      if (a.q_cf) {
+        a.q_cf[(b * a.C2 + c2) * a.T + t] = v;
+      } else if (c2 < a.t_split) {
+        a.t_cf0[(b * a.t_split + c2) * a.T + t] = v;
+      } else {
+        const int ns = a.C2 - a.t_split;
+        a.t_cf1[(b * ns + c2 - a.t_split) * a.T + t] = v;
+      }
+    }
+  }
 }
 
 template <int WAVES_M, int WAVES_N, int WM, int WN, int KCH>
@@ -182,75 +249,22 @@ __global__ __launch_bounds__(256) void conv_mm_kernel(ConvArgs a) {
     }
   }
   if (!a.tW) return;
-  // ---- fused 1x1 tail: z = tW @ y + tb (and softmax over C2), thread per row
-  float* Zs = smem + BM * LDY;  // [BM][C2 + 1]
-  const int LDZ = a.C2 + 1;
-  for (int row = tid; row < BM; row += 256) {
-    const int64_t r = m0 + row;
-    int64_t b;
-    int t;
-    const bool valid = row_bt(r, a.R, a.T, b, t);
-    float mx = -__builtin_inff();
-    for (int c2 = 0; c2 < a.C2; ++c2) {
-      float z = 0.f;
-      if (valid) {
-        z = a.tb ? a.tb[c2] : 0.f;
-        const float* w = a.tW + (int64_t)c2 * a.N;
-        for (int n = 0; n < a.N; ++n) z = fmaf(w[n], Ys[row * LDY + n], z);
-      }
-      Zs[row * LDZ + c2] = z;
-      mx = fmaxf(mx, z);
-      if (a.t_out && r < a.R) a.t_out[r * ld4(a.C2) + c2] = z;
-    }
-    for (int c2 = a.C2; c2 < ld4(a.C2); ++c2) {
-      if (a.t_out && r < a.R) a.t_out[r * ld4(a.C2) + c2] = 0.f;
-      if (a.q_out && r < a.R) a.q_out[r * ld4(a.C2) + c2] = 0.f;
-    }
-    if (a.q_out || a.q_cf || a.reg_out) {
-      float s = 0.f;
-      for (int c2 = 0; c2 < a.C2; ++c2) s += __expf(Zs[row * LDZ + c2] - mx);
-      float bq = -__builtin_inff();
-      int bi = 0x7fffffff;
-      for (int c2 = 0; c2 < a.C2; ++c2) {
-        const float q = valid ? __expf(Zs[row * LDZ + c2] - mx) / s : 0.f;
-        if (a.q_out && r < a.R) a.q_out[r * ld4(a.C2) + c2] = q;
-        if (a.q_cf) Zs[row * LDZ + c2] = q;
-        if (argmax_beats(q, c2, bq, bi)) { bq = q; bi = c2; }
-      }
-      if (a.reg_out && valid) a.reg_out[b * a.T + t] = bi;  // hard regime (backtesting.py:154-155)
-    }
-  }
-  if (a.t_cf0 || a.q_cf) {
-    __syncthreads();
-    for (int i = tid; i < BM * a.C2; i += 256) {
-      const int row = i % BM, c2 = i / BM;
-      const int64_t r = m0 + row;
-      int64_t b;
-      int t;
-      if (!row_bt(r, a.R, a.T, b, t)) continue;
-      const float v = Zs[row * LDZ + c2];
-      if (a.q_cf) {
-        a.q_cf[(b * a.C2 + c2) * a.T + t] = v;
-      } else if (c2 < a.t_split) {
-        a.t_cf0[(b * a.t_split + c2) * a.T + t] = v;
-      } else {
-        const int ns = a.C2 - a.t_split;
-        a.t_cf1[(b * ns + c2 - a.t_split) * a.T + t] = v;
-      }
-    }
-  }
+  // ---- fused 1x1 tail on the activated tile
+  conv_tail_rows(a, Ys, LDY, m0, BM, smem + BM * LDY);
+}
+
+// The same tail as a launch of its own over the activation a conv without the tail stored (a.out): layers wider
+// than the widest tile (N > 256), whose rows no single workgroup holds.  256 rows per workgroup.
+__global__ __launch_bounds__(256) void conv_tail_kernel(ConvArgs a) {
+  extern __shared__ float4 smem4[];
+  const int64_t m0 = (int64_t)blockIdx.x * 256;
+  conv_tail_rows(a, a.out + m0 * ld4(a.N), ld4(a.N), m0, 256, reinterpret_cast<float*>(smem4));
 }
 
 template <int WAVES_M, int WAVES_N, int WM, int WN, int KCH>
-static int launch_conv_cfg(const ConvArgs& a, hipStream_t s) {
+static int launch_conv_cfg(const ConvArgs& a, size_t lds, hipStream_t s) {
   constexpr int BM = WAVES_M * WM * 16;
   constexpr int BN = WAVES_N * WN * 16;
-  const size_t main_lds = ((size_t)(BM + 2) * (KCH + 4) + (size_t)a.ks * BN * (KCH + 4)) * 4;
-  size_t epi_lds = (size_t)BM * (BN + 4) * 4;
-  if (a.tW) epi_lds += (size_t)BM * (a.C2 + 1) * 4;
-  const size_t lds = main_lds > epi_lds ? main_lds : epi_lds;
-  if (lds > 160 * 1024) return VQHMM_EUNSUPPORTED;
-  if (a.tW && a.N > BN) return VQHMM_EUNSUPPORTED;
   const dim3 grid((unsigned)cdiv(a.R, BM), (unsigned)cdiv(a.N, BN));
   conv_mm_kernel<WAVES_M, WAVES_N, WM, WN, KCH><<<grid, 256, lds, s>>>(a);
   VQHMM_LAUNCH_CHECK();
@@ -272,21 +286,84 @@ static bool convbig_split(const ConvArgs& a, ConvArgs& main, ConvArgs& tail) {
   return convbig_supported(tail);
 }
 
+// conv_mm_kernel's tiles (BM rows x BN outputs, KCH-channel slices), in conv_choice's cfg order
+static const int kConvMmCfg[9][3] = {{256, 16, 16}, {256, 16, 32}, {256, 32, 16}, {256, 32, 32}, {128, 64, 16},
+                                     {128, 64, 32}, {64, 128, 16}, {64, 128, 32}, {64, 256, 16}};
+
+ConvChoice conv_choice(const ConvArgs& a) {
+  ConvChoice c{CONV_UNSUPPORTED, 0, 0};
+  if (a.Kc <= 0 || a.N <= 0 || (a.ks != 1 && a.ks != 3)) return c;
+  if (conv2_supported(a)) { c.kind = CONV_CONV2; return c; }
+  ConvArgs cm, ct;
+  if (convbig_split(a, cm, ct)) { c.kind = a.tW ? CONV_BIG_TAIL : CONV_BIG; return c; }
+  const int wide = a.Kc > 16;
+  c.cfg = a.N <= 16 ? 0 + wide : a.N <= 32 ? 2 + wide : a.N <= 64 ? 4 + wide : a.N <= 128 ? 6 + wide : 8;
+  const int BM = kConvMmCfg[c.cfg][0], BN = kConvMmCfg[c.cfg][1], KCH = kConvMmCfg[c.cfg][2];
+  const size_t main_lds = ((size_t)(BM + 2) * (KCH + 4) + (size_t)a.ks * BN * (KCH + 4)) * 4;
+  const size_t epi_lds = (size_t)BM * (BN + 4) * 4, tail_lds = (size_t)BM * (a.C2 + 1) * 4;
+  // a layer wider than the widest tile (N > 256), or a tail whose rows do not fit the LDS beside the tile (256-row
+  // tiles: C2 > 139 beside 16 outputs, > 123 beside 32): the conv without the tail, then conv_tail_kernel over
+  // the stored activation
+  const bool split = a.tW && (a.N > BN || epi_lds + tail_lds > 160 * 1024);
+  if (split && !a.out) return c;
+  c.lds = std::max(main_lds, epi_lds + (a.tW && !split ? tail_lds : 0));
+  if (c.lds > 160 * 1024 || (split && (size_t)256 * (a.C2 + 1) * 4 > 160 * 1024)) return c;
+  c.kind = split ? CONV_MM_TAIL_SPLIT : a.tW ? CONV_MM_TAIL : CONV_MM;
+  return c;
+}
+
+void conv_family(const ConvArgs& a, char* out, size_t n) {
+  const ConvChoice c = conv_choice(a);
+  const int* t = kConvMmCfg[c.cfg];
+  switch (c.kind) {
+    case CONV_CONV2: snprintf(out, n, "conv2"); break;
+    case CONV_BIG: snprintf(out, n, "convbig"); break;
+    case CONV_BIG_TAIL: snprintf(out, n, "convbig+tail"); break;
+    case CONV_MM: snprintf(out, n, "conv_mm<%d,%d,%d>", t[0], t[1], t[2]); break;
+    case CONV_MM_TAIL: snprintf(out, n, "conv_mm<%d,%d,%d>+tail", t[0], t[1], t[2]); break;
+    case CONV_MM_TAIL_SPLIT: snprintf(out, n, "conv_mm<%d,%d,%d>+tail_kernel", t[0], t[1], t[2]); break;
+    default: snprintf(out, n, "unsupported"); break;
+  }
+}
+
+static int launch_conv_mm(const ConvArgs& a, const ConvChoice& c, hipStream_t s) {
+  switch (c.cfg) {
+    case 0: return launch_conv_cfg<4, 1, 4, 1, 16>(a, c.lds, s);
+    case 1: return launch_conv_cfg<4, 1, 4, 1, 32>(a, c.lds, s);
+    case 2: return launch_conv_cfg<4, 1, 4, 2, 16>(a, c.lds, s);
+    case 3: return launch_conv_cfg<4, 1, 4, 2, 32>(a, c.lds, s);
+    case 4: return launch_conv_cfg<2, 2, 4, 2, 16>(a, c.lds, s);
+    case 5: return launch_conv_cfg<2, 2, 4, 2, 32>(a, c.lds, s);
+    case 6: return launch_conv_cfg<1, 4, 4, 2, 16>(a, c.lds, s);
+    case 7: return launch_conv_cfg<1, 4, 4, 2, 32>(a, c.lds, s);
+    default: return launch_conv_cfg<1, 4, 4, 4, 16>(a, c.lds, s);
+  }
+}
+
 int launch_conv(const ConvArgs& a, hipStream_t s) {
   if (a.R == 0) return VQHMM_OK;
   if (!a.src || !a.W || a.Kc <= 0 || a.N <= 0 || (a.ks != 1 && a.ks != 3)) return VQHMM_EINVAL;
-  if (conv2_supported(a)) return launch_conv2(a, s);
-  ConvArgs cm, ct;
-  if (convbig_split(a, cm, ct)) {
-    if (int rc = launch_convbig(cm, s)) return rc;
-    return a.tW ? launch_convbig(ct, s) : VQHMM_OK;
+  const ConvChoice c = conv_choice(a);
+  switch (c.kind) {
+    case CONV_CONV2: return launch_conv2(a, s);
+    case CONV_BIG: case CONV_BIG_TAIL: {
+      ConvArgs cm, ct;
+      convbig_split(a, cm, ct);
+      if (int rc = launch_convbig(cm, s)) return rc;
+      return a.tW ? launch_convbig(ct, s) : VQHMM_OK;
+    }
+    case CONV_MM: case CONV_MM_TAIL: return launch_conv_mm(a, c, s);
+    case CONV_MM_TAIL_SPLIT: {
+      ConvArgs cm = a;
+      cm.tW = nullptr; cm.tb = nullptr; cm.C2 = 0; cm.t_out = nullptr; cm.t_cf0 = nullptr; cm.t_cf1 = nullptr;
+      cm.t_split = 0; cm.q_out = nullptr; cm.q_cf = nullptr; cm.reg_out = nullptr;
+      if (int rc = launch_conv_mm(cm, c, s)) return rc;
+      conv_tail_kernel<<<(unsigned)cdiv(a.R, 256), 256, (size_t)256 * (a.C2 + 1) * 4, s>>>(a);
+      VQHMM_LAUNCH_CHECK();
+      return VQHMM_OK;
+    }
   }
-  const bool wide = a.Kc > 16;
-  if (a.N <= 16) return wide ? launch_conv_cfg<4, 1, 4, 1, 32>(a, s) : launch_conv_cfg<4, 1, 4, 1, 16>(a, s);
-  if (a.N <= 32) return wide ? launch_conv_cfg<4, 1, 4, 2, 32>(a, s) : launch_conv_cfg<4, 1, 4, 2, 16>(a, s);
-  if (a.N <= 64) return wide ? launch_conv_cfg<2, 2, 4, 2, 32>(a, s) : launch_conv_cfg<2, 2, 4, 2, 16>(a, s);
-  if (a.N <= 128) return wide ? launch_conv_cfg<1, 4, 4, 2, 32>(a, s) : launch_conv_cfg<1, 4, 4, 2, 16>(a, s);
-  return launch_conv_cfg<1, 4, 4, 4, 16>(a, s);
+  return VQHMM_EUNSUPPORTED;
 }
 
 // ------------------------------------------------------------------ wgrad
@@ -406,12 +483,27 @@ int64_t wgrad_chunks(int64_t R, int64_t tiles) {
   return rows;
 }
 
+int wgrad_choice(const WgradArgs& a) {
+  if (a.ks != 1 && a.ks != 3) return WGRAD_UNSUPPORTED;
+  return wgrad2_supported(a) ? WGRAD_2 : wgradbig_supported(a) ? WGRAD_BIG : WGRAD_GENERIC;
+}
+
+const char* wgrad_family(const WgradArgs& a) {
+  switch (wgrad_choice(a)) {
+    case WGRAD_2: return "wgrad2";
+    case WGRAD_BIG: return "wgradbig";
+    case WGRAD_GENERIC: return "wgrad_generic";
+  }
+  return "unsupported";
+}
+
 int launch_wgrad(const WgradArgs& a0, hipStream_t s) {
   WgradArgs a = a0;
   if (a.R == 0) return VQHMM_OK;
   if (!a.dy || !a.x || !a.slab || (a.ks != 1 && a.ks != 3) || a.rows_per_chunk % 64) return VQHMM_EINVAL;
-  if (wgrad2_supported(a)) return launch_wgrad2(a, s);
-  if (wgradbig_supported(a)) return launch_wgradbig(a, s);
+  const int kind = wgrad_choice(a);
+  if (kind == WGRAD_2) return launch_wgrad2(a, s);
+  if (kind == WGRAD_BIG) return launch_wgradbig(a, s);
   const int64_t nchunks = cdiv(a.R, a.rows_per_chunk);
   constexpr int TN = 64, TC = 64;
   const dim3 grid((unsigned)(cdiv(a.N, TN) * cdiv(a.C, TC)), (unsigned)nchunks);

@@ -380,16 +380,21 @@ int head_grid(int64_t R) {
   return (int)(ntiles < 512 ? ntiles : 512);
 }
 
-bool fused_head_supported(const HeadArgs& a) {
-  return head_mfma_supported(a) || (a.K <= 8 && a.U <= 8 && a.TH <= 256 && a.D <= 16);
+// launch_head's kernel: the tile-barrier MFMA head where it applies, else the scalar head (thread per row)
+int fused_head_kind(const HeadArgs& a) {
+  if (head_mfma_supported(a)) return HEAD_MFMA;
+  return (a.K <= 8 && a.U <= 8 && a.TH <= 256 && a.D <= 16) ? HEAD_SCALAR : HEAD_NONE;
 }
+
+bool fused_head_supported(const HeadArgs& a) { return fused_head_kind(a) != HEAD_NONE; }
 
 int launch_head(const HeadArgs& a0, int grid, hipStream_t s) {
   HeadArgs a = a0;
   a.ntiles = cdiv(a.R, HP);
   if (a.R == 0) return VQHMM_OK;
-  if (head_mfma_supported(a)) return launch_head_mfma(a, grid, s);
-  if (a.K > 8 || a.U > 8 || a.TH > 256 || a.D > 16) return VQHMM_EUNSUPPORTED;
+  const int kind = fused_head_kind(a);
+  if (kind == HEAD_MFMA) return launch_head_mfma(a, grid, s);
+  if (kind != HEAD_SCALAR) return VQHMM_EUNSUPPORTED;
   if (a.K <= 4)
     elbo_head_kernel<4, 8><<<grid, 256, 0, s>>>(a);
   else

@@ -492,17 +492,40 @@ __global__ void log_softmax_small_kernel(const float* v, int K, float* out) {
 
 bool staged_head_supported(int K) { return K >= 1 && K <= 64; }  // lane = state (head_l1 / head_l2)
 
+// the staged head's first row kernel by K (launch_staged_head and the family query)
+int staged_l1_variant(int K) {
+  if (!staged_head_supported(K)) return L1_NONE;
+  if (K <= 8) return L1_LANES16;
+  if (K == 32) return L1_POW2_32;
+  if (K == 16) return L1_POW2_16;
+  if (K <= 32) return K % 4 == 0 ? L1_WIDE4 : L1_WIDE;
+  return L1_LANES64;
+}
+const char* staged_l1_name(int K) {
+  switch (staged_l1_variant(K)) {
+    case L1_LANES16: return "l1<16>";
+    case L1_POW2_32: return "l1_pow2<32>";
+    case L1_POW2_16: return "l1_pow2<16>";
+    case L1_WIDE4: return "l1_wide<4>";
+    case L1_WIDE: return "l1_wide<1>";
+    case L1_LANES64: return "l1<64>";
+  }
+  return "unsupported";
+}
+
 int launch_staged_head(const StagedHeadArgs& a, int l2grid, hipStream_t s) {
   if (!staged_head_supported(a.K)) return VQHMM_EUNSUPPORTED;
   log_softmax_small_kernel<<<1, 64, 0, s>>>(a.log_prior, a.K, a.log_pi);
   VQHMM_LAUNCH_CHECK();
   const unsigned g1 = (unsigned)std::min<int64_t>(cdiv(a.R, 4), 2048);
-  if (a.K <= 8) head_l1_kernel<16><<<g1, 256, 0, s>>>(a);
-  else if (a.K == 32) head_l1_pow2_kernel<32><<<g1, 256, 0, s>>>(a);
-  else if (a.K == 16) head_l1_pow2_kernel<16><<<g1, 256, 0, s>>>(a);
-  else if (a.K <= 32 && a.K % 4 == 0) head_l1_wide_kernel<true><<<g1, 256, 0, s>>>(a);
-  else if (a.K <= 32) head_l1_wide_kernel<false><<<g1, 256, 0, s>>>(a);
-  else head_l1_kernel<64><<<g1, 256, 0, s>>>(a);
+  switch (staged_l1_variant(a.K)) {
+    case L1_LANES16: head_l1_kernel<16><<<g1, 256, 0, s>>>(a); break;
+    case L1_POW2_32: head_l1_pow2_kernel<32><<<g1, 256, 0, s>>>(a); break;
+    case L1_POW2_16: head_l1_pow2_kernel<16><<<g1, 256, 0, s>>>(a); break;
+    case L1_WIDE4: head_l1_wide_kernel<true><<<g1, 256, 0, s>>>(a); break;
+    case L1_WIDE: head_l1_wide_kernel<false><<<g1, 256, 0, s>>>(a); break;
+    default: head_l1_kernel<64><<<g1, 256, 0, s>>>(a); break;
+  }
   VQHMM_LAUNCH_CHECK();
   head_l2_kernel<<<l2grid, L2_NT, 0, s>>>(a);
   VQHMM_LAUNCH_CHECK();

@@ -213,6 +213,17 @@ size_t vq_quantize_ws_bytes(int64_t B, int64_t Dv, int64_t T, int64_t K);
 int launch_vq_quantize(const float* z, int64_t B, int64_t Dv, int64_t T, const float* cb, int64_t K, int32_t* idx,
                        float* zq_st, double* sse, void* ws, size_t ws_bytes, hipStream_t s);
 int launch_conv(const ConvArgs& a, hipStream_t s);
+// launch_conv's kernel choice, a pure function of the shapes and of which outputs are asked for (the launcher
+// and the family query, vqhmm_elbo_stage_family, both go through it)
+enum ConvKind { CONV_UNSUPPORTED, CONV_CONV2, CONV_BIG, CONV_BIG_TAIL, CONV_MM, CONV_MM_TAIL, CONV_MM_TAIL_SPLIT };
+struct ConvChoice {
+  int kind;    // ConvKind
+  int cfg;     // CONV_MM*: conv_mm_kernel's tile configuration (conv.hip kConvMmCfg)
+  size_t lds;  // ... and its dynamic LDS bytes
+};
+ConvChoice conv_choice(const ConvArgs& a);
+// "conv2", "convbig", "convbig+tail", "conv_mm<BM,BN,KCH>[+tail | +tail_kernel]" or "unsupported"
+void conv_family(const ConvArgs& a, char* out, size_t n);
 // wide convolutions and weight gradients on the f32 MFMA (convbig.hip): Kc % 16 == 0, N % 4 == 0, PCL in / out
 bool convbig_supported(const ConvArgs& a);
 int launch_convbig(const ConvArgs& a, hipStream_t s);
@@ -285,6 +296,10 @@ int conv2_prof_copy(uint64_t* out, int64_t n);
 int head_prof_copy(uint64_t* out, int64_t n);  // head_coop.hip (VQHMM_HEAD_PROF)
 int bwdw_prof_copy(uint64_t* out, int64_t n);  // strip_bwdw.hip (VQHMM_STRIP_PROF)
 int launch_wgrad(const WgradArgs& a, hipStream_t s);
+// launch_wgrad's kernel choice (shapes only) and its family name: "wgrad2", "wgradbig", "wgrad_generic"
+enum WgradKind { WGRAD_UNSUPPORTED, WGRAD_2, WGRAD_BIG, WGRAD_GENERIC };
+int wgrad_choice(const WgradArgs& a);
+const char* wgrad_family(const WgradArgs& a);
 bool wgradbig_supported(const WgradArgs& a);
 int64_t wgradbig_rows(int64_t R, int N, int C);
 int launch_wgradbig(const WgradArgs& a, hipStream_t s);
@@ -327,6 +342,13 @@ struct StagedHeadArgs {
 };
 bool staged_head_supported(int K);
 bool fused_head_supported(const HeadArgs& a);
+// launch_head's kernel (head.hip): the tile-barrier MFMA head or the scalar head
+enum FusedHeadKind { HEAD_NONE, HEAD_MFMA, HEAD_SCALAR };
+int fused_head_kind(const HeadArgs& a);
+// launch_staged_head's first row kernel by K, and its name ("l1<16>", "l1_pow2<32>", "l1_wide<4>", ...)
+enum StagedL1 { L1_NONE, L1_LANES16, L1_POW2_32, L1_POW2_16, L1_WIDE4, L1_WIDE, L1_LANES64 };
+int staged_l1_variant(int K);
+const char* staged_l1_name(int K);
 int launch_staged_head(const StagedHeadArgs& a, int l2grid, hipStream_t s);
 
 int head_grid(int64_t R);

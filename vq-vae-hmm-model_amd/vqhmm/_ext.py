@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # VQHMM_LIB_PATH: load another build of the same library (kernel A/B experiments only)
 LIB_PATH = os.environ.get("VQHMM_LIB_PATH") or os.path.join(_HERE, "libvqhmm.so")
 NPARAMS = 18
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 EUNSUPPORTED = -4
 _ERRORS = {-1: "invalid argument", -2: "kernel launch failed", -3: "workspace too small",
@@ -70,6 +70,7 @@ _SIGS = {
     "vqhmm_elbo_stage_info": (ctypes.c_int, [ctypes.POINTER(Dims), c_i64, c_i64, ctypes.c_int, ctypes.c_char_p, c_sz,
                                              ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                              ctypes.POINTER(ctypes.c_int)]),
+    "vqhmm_elbo_stage_family": (ctypes.c_int, [ctypes.POINTER(Dims), c_i64, c_i64, ctypes.c_int, ctypes.c_char_p, c_sz]),
     "vqhmm_elbo_stage_f32": (ctypes.c_int, [ctypes.POINTER(Dims), ctypes.POINTER(c_vp), c_vp, c_vp, ctypes.c_int,
                                             c_vp, c_vp, c_i64, c_i64, c_f32, c_vp, c_sz, c_vp, ctypes.c_int, c_vp]),
     "vqhmm_clip_grad_norm_f32": (ctypes.c_int, [c_vp, c_i64, c_f32, c_f32, c_vp, c_vp]),
