@@ -157,6 +157,54 @@ int vqhmm_fwdbwd_xi_f32(const float* log_pi, const float* log_A, const float* em
                         int64_t B, int64_t T, int64_t K, float* gamma, float* xi, float* logZ,
                         void* workspace, size_t ws_bytes, void* stream);
 
+/* ----------------------------------------------- HMM on VQ code indices ----
+ * The stationary discrete HMM of the pipeline's second half (pseudocode.txt:25-32: hmm.train_em on
+ * the collected code indices, hmm.sample; math.md:23-62 with M_t = M; hmm_code.hip):
+ * log_pi (S), log_A (S,S) with log_A[i,j] = log p(z_t = j | z_{t-1} = i), log_B (S,V) with
+ * log_B[s,v] = log p(code = v | z = s), all fp32 natural logs; rows need not be normalised and
+ * -inf is a structural zero.  1 <= S <= 32, 1 <= V <= 65536 (else VQHMM_EUNSUPPORTED, and the
+ * workspace query returns 0).  codes (B,T) int32 as vqhmm_vq_argmin_f32 writes them, lengths (B)
+ * int64 clamped to [0, T]; codes at t >= length are never interpreted.
+ *
+ * vqhmm_code_estep_f32: the Baum-Welch E-step in one call.  Every element of
+ *   pi_cnt (S)      = sum_b gamma_{b,0}(s)
+ *   trans_cnt (S,S) = sum_b sum_{1 <= t < L_b} xi_{b,t}(i,j)
+ *   emit_cnt (S,V)  = sum_b sum_{t < L_b, codes[b,t] = v} gamma_{b,t}(s)
+ * is written, in fp64 (the caller never clears them).  loglik (B) fp32 = log p(codes_{b,0:L_b})
+ * (NaN for length 0) and gamma (B,T,S) fp32 (rows at t >= L are 0) are nullable; with gamma NULL
+ * nothing of size B*T*S is written as output.  Neither per-step tables nor xi are materialised: the
+ * chain runs on linear probabilities normalised at every step with the transition matrix in
+ * registers and exp(log_B)^T in LDS (read through L2 when it does not fit), the step masses' logs
+ * are summed in fp64, and a step whose mass leaves [2^-30, 2^30] is redone max-shifted in natural
+ * log.  An impossible sequence (mass truly 0) gets loglik = -inf and a sequence with a code outside
+ * [0, V) inside its length gets loglik = NaN; both contribute exactly 0 to every count, have zero
+ * gamma rows and leave the other sequences untouched (log_B is never read out of range).
+ * Deterministic: sequences are assigned to waves statically, each wave sums into a private slab and
+ * the slabs are added in a fixed order in fp64; no float atomics.  Graph-capturable, no host sync.
+ * B*T == 0 returns VQHMM_OK with the counts zeroed (and loglik = NaN for B > 0).
+ * Workspace: vqhmm_code_estep_workspace_size(B, T, S, V) bytes (the scaled forward vectors,
+ * 4*S bytes per position, the emission table and the slabs).
+ * Accuracy target vs the fp64 oracle, per position: |gamma| abs 1e-5, |xi| abs 2e-5 (the counts
+ * are their sums), loglik rel 1e-5 of max(1, |loglik|).
+ * Reads stay inside [0, B*T) of codes and inside the parameter arrays.
+ *
+ * vqhmm_code_sample_f32: ancestral sampling of N sequences of length T by inverse CDF from
+ * caller-supplied uniforms (N,T,2) fp32 in [0,1): uniforms[n,t,0] draws z_t (from pi at t = 0, from
+ * row z_{t-1} of A afterwards), uniforms[n,t,1] draws the code from row z_t of B.  The rule is part
+ * of the contract: p_k = exp(log p_k) in fp32, cdf_k = the fp32 running sum in index order divided
+ * by its own total, the draw is the first k with u < cdf_k, or the last k with p_k > 0 if there is
+ * none; a zero-probability category is never drawn.  states (N,T), codes (N,T) int32.  No workspace. */
+size_t vqhmm_code_estep_workspace_size(int64_t B, int64_t T, int64_t S, int64_t V);
+int vqhmm_code_estep_f32(const float* log_pi, const float* log_A, const float* log_B,
+                         const int32_t* codes, const int64_t* lengths,
+                         int64_t B, int64_t T, int64_t S, int64_t V,
+                         double* pi_cnt, double* trans_cnt, double* emit_cnt,
+                         float* loglik, float* gamma,
+                         void* workspace, size_t ws_bytes, void* stream);
+int vqhmm_code_sample_f32(const float* log_pi, const float* log_A, const float* log_B,
+                          const float* uniforms, int64_t N, int64_t T, int64_t S, int64_t V,
+                          int32_t* states, int32_t* codes, void* stream);
+
 /* ------------------------------------------------------- training step ----
  * compute_loss forward + backward of VAE_HMM (VQ_VAE_HMM_fixed.py:106-137,
  * autograd of :156) as one native executor over hand-written kernels.

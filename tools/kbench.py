@@ -2,6 +2,9 @@
 
     python tools/kbench.py vq [--B 2048 --Dv 64 --T 200 --K 32]
     python tools/kbench.py xi --B 512 --T 512 --K 8     (fwdbwd, filter, xi, combined; alternated)
+    python tools/kbench.py estep --B 1024 --T 512 --K 8 --V 512 [--old-route]
+                                                        (the fused E-step on code indices; --old-route: also
+                                                         the same statistics through pairwise_posteriors)
 """
 import argparse
 import json
@@ -170,6 +173,67 @@ def bench_xi(a):
                           "frac_hbm": byts[k] / t[k] / HBM_PEAK, "x_fwdbwd": t[k] / t["fwdbwd"]}))
 
 
+def bench_estep(a):
+    """vqhmm_code_estep_f32 (counts + loglik, no gamma) at S = --K states, V = --V codes.  --old-route: also the
+    existing entry points' way to the same statistics (broadcast log_A, the log_B[:, codes] gather,
+    pairwise_posteriors, then xi.sum, gamma[:, 0].sum and index_add_), alternated with the new call (median of
+    the rounds).  Algorithmic HBM bytes per position: the code (4) and the scaled forward vector written and
+    read back (8 S); the old route's: 4 S^2 (log_A) + 4 S (em) written, read by three kernels, + xi."""
+    B, T, S, V = a.B, a.T, a.K, a.V
+    g = torch.Generator(device="cuda").manual_seed(11)
+    hmm = vqhmm.CodeHMM(S, V, generator=torch.Generator().manual_seed(3)).cuda()
+    codes = torch.randint(0, V, (B, T), device="cuda", generator=g, dtype=torch.int32)
+    L = torch.full((B,), T, dtype=torch.int64, device="cuda")
+    lib = vqhmm._ext.load()
+    P = vqhmm._ext.ptr
+    st = vqhmm._ext.stream_ptr()
+    cnt = [torch.empty(n, dtype=torch.float64, device="cuda") for n in (S, S * S, S * V)]
+    ll = torch.empty(B, device="cuda")
+    nb = lib.vqhmm_code_estep_workspace_size(B, T, S, V)
+    ws = torch.empty(max(nb, 1), dtype=torch.uint8, device="cuda")
+
+    def new():
+        lib.vqhmm_code_estep_f32(P(hmm.log_pi), P(hmm.log_A), P(hmm.log_B), P(codes), P(L), B, T, S, V, P(cnt[0]),
+                                 P(cnt[1]), P(cnt[2]), P(ll), None, P(ws), nb, st)
+
+    cl = codes.long()
+
+    def old():
+        log_A = hmm.log_A.expand(B, T, S, S)
+        em = hmm.log_B[:, cl].permute(1, 2, 0)
+        gamma, xi, logZ = vqhmm.pairwise_posteriors(hmm.log_pi, log_A, em, L)
+        trans = xi.sum((0, 1), dtype=torch.float64)
+        pi = gamma[:, 0].sum(0, dtype=torch.float64)
+        emit = torch.zeros(V, S, dtype=torch.float64, device="cuda").index_add_(0, cl.reshape(-1),
+                                                                               gamma.reshape(-1, S).double())
+        return pi, trans, emit, logZ
+
+    legs = {"code_estep": new}
+    if a.old_route:
+        legs["old_route"] = old
+        pi, trans, emit, _ = old()
+        new()
+        torch.cuda.synchronize()
+        print(json.dumps({"check": "old_route vs code_estep", "trans_maxdiff": (trans.reshape(-1) - cnt[1]).abs().max().item(),
+                          "emit_maxdiff": (emit.t().reshape(-1) - cnt[2]).abs().max().item(),
+                          "pi_maxdiff": (pi - cnt[0]).abs().max().item()}))
+    for fn in legs.values():
+        time_fn(fn, iters=3, warmup=2)
+    rounds = {k: [] for k in legs}
+    for _ in range(7):
+        for k, fn in legs.items():
+            rounds[k].append(time_fn(fn, iters=10, warmup=1))
+    t = {k: sorted(v)[len(v) // 2] for k, v in rounds.items()}
+    n = B * T
+    byts = {"code_estep": n * (4 + 8 * S), "old_route": n * (4 * S * S * (1 + 3 + 2 + 1) + 4 * S * (1 + 3 + 2 + 2))}
+    for k in legs:
+        rec = {"kernel": k, "B": B, "T": T, "S": S, "V": V, "us": t[k] * 1e6, "min_us": min(rounds[k]) * 1e6,
+               "max_us": max(rounds[k]) * 1e6, "GBps": byts[k] / t[k] / 1e9, "frac_hbm": byts[k] / t[k] / HBM_PEAK}
+        if k == "old_route":
+            rec["x_code_estep"] = t[k] / t["code_estep"]
+        print(json.dumps(rec))
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("what")
@@ -177,6 +241,8 @@ if __name__ == "__main__":
     ap.add_argument("--Dv", type=int, default=64)
     ap.add_argument("--T", type=int, default=200)
     ap.add_argument("--K", type=int, default=32)
+    ap.add_argument("--V", type=int, default=512)
+    ap.add_argument("--old-route", action="store_true")
     a = ap.parse_args()
     {"vq": bench_vq, "stream": bench_stream, "viterbi": bench_viterbi, "fwdbwd": bench_fwdbwd,
-     "filter": bench_filter, "xi": bench_xi}[a.what](a)
+     "filter": bench_filter, "xi": bench_xi, "estep": bench_estep}[a.what](a)

@@ -384,6 +384,32 @@ int vqhmm_fwdbwd_xi_f32(const float* log_pi, const float* log_A, const float* em
   return launch_hmm_xi(log_A, filt, gamma, lengths, B, T, K, xi, s);
 }
 
+size_t vqhmm_code_estep_workspace_size(int64_t B, int64_t T, int64_t S, int64_t V) {
+  return hmm_code_estep_ws_bytes(B, T, S, V);
+}
+
+int vqhmm_code_estep_f32(const float* log_pi, const float* log_A, const float* log_B, const int32_t* codes,
+                         const int64_t* lengths, int64_t B, int64_t T, int64_t S, int64_t V, double* pi_cnt,
+                         double* trans_cnt, double* emit_cnt, float* loglik, float* gamma, void* ws, size_t ws_bytes,
+                         void* stream) {
+  if (B < 0 || T < 0 || S < 1 || V < 1 || !log_pi || !log_A || !log_B || !pi_cnt || !trans_cnt || !emit_cnt ||
+      (B > 0 && !lengths) || (B * T > 0 && !codes))
+    return VQHMM_EINVAL;
+  if (!hmm_code_supported(S, V)) return VQHMM_EUNSUPPORTED;
+  if (B * T > 0 && (!ws || ws_bytes < hmm_code_estep_ws_bytes(B, T, S, V))) return VQHMM_EWORKSPACE;
+  return launch_hmm_code_estep(log_pi, log_A, log_B, codes, lengths, B, T, S, V, pi_cnt, trans_cnt, emit_cnt, loglik,
+                               gamma, ws, (hipStream_t)stream);
+}
+
+int vqhmm_code_sample_f32(const float* log_pi, const float* log_A, const float* log_B, const float* uniforms,
+                          int64_t N, int64_t T, int64_t S, int64_t V, int32_t* states, int32_t* codes, void* stream) {
+  if (N < 0 || T < 0 || S < 1 || V < 1 || !log_pi || !log_A || !log_B ||
+      (N * T > 0 && (!uniforms || !states || !codes)))
+    return VQHMM_EINVAL;
+  if (!hmm_code_supported(S, V)) return VQHMM_EUNSUPPORTED;
+  return launch_hmm_code_sample(log_pi, log_A, log_B, uniforms, N, T, S, V, states, codes, (hipStream_t)stream);
+}
+
 int vqhmm_elbo_workspace_size(const vqhmm_dims_t* d, int64_t B, int64_t T, size_t* bytes) {
   if (!dims_ok(d) || B < 0 || T < 0 || !bytes) return VQHMM_EINVAL;
   *bytes = plan_elbo(d, B, T, nullptr).bytes;

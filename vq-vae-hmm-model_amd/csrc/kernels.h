@@ -501,6 +501,16 @@ int launch_hmm_filter(const float* log_pi, const float* log_A, const float* em, 
                       int64_t T, int64_t K, float* filt, float* loglik, hipStream_t s);
 int launch_hmm_xi(const float* log_A, const float* filt, const float* gamma, const int64_t* lengths, int64_t B,
                   int64_t T, int64_t K, float* xi, hipStream_t s);
+// stationary HMM on code indices, 1 <= S <= 32, 1 <= V <= 65536 (hmm_code.hip): the fused E-step (counts in
+// fp64, loglik and gamma nullable; ws = hmm_code_estep_ws_bytes) and the inverse-CDF ancestral sampler
+bool hmm_code_supported(int64_t S, int64_t V);
+size_t hmm_code_estep_ws_bytes(int64_t B, int64_t T, int64_t S, int64_t V);
+int launch_hmm_code_estep(const float* log_pi, const float* log_A, const float* log_B, const int32_t* codes,
+                          const int64_t* lengths, int64_t B, int64_t T, int64_t S, int64_t V, double* pi_cnt,
+                          double* trans_cnt, double* emit_cnt, float* loglik, float* gamma, void* ws, hipStream_t s);
+int launch_hmm_code_sample(const float* log_pi, const float* log_A, const float* log_B, const float* uniforms,
+                           int64_t N, int64_t T, int64_t S, int64_t V, int32_t* states, int32_t* codes,
+                           hipStream_t s);
 int launch_clip_grad_norm(float* g, int64_t n, float pre_scale, float max_norm, float* total_out, hipStream_t s);
 int launch_adam(float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2,
                 double eps, int64_t* step, float gmul, hipStream_t s);

@@ -1,0 +1,154 @@
+"""Stationary HMM on VQ code indices: Baum-Welch EM and ancestral sampling
+(pseudocode.txt:25-32: `hmm.train_em(all_code_indices)`, `hmm.sample(seq_len)`; math.md:23-62 with
+M_t = M).  HIP only: the E-step and the sampler are the fused kernels of hmm_code.hip
+(vqhmm_code_estep_f32 / vqhmm_code_sample_f32, contracts in include/vqhmm.h); the M-step is
+S*S + S*V numbers of torch arithmetic in fp64 on the device.
+"""
+import torch
+
+from . import _ext
+
+MAX_STATES = 32      # the kernels' limits (hmm_code.hip)
+MAX_CODES = 65536
+
+
+def _row_log_normalise(w):
+    return torch.log(w / w.sum(-1, keepdim=True)).float()
+
+
+class CodeHMM(torch.nn.Module):
+    """HMM with `num_states` hidden states emitting one of `num_codes` VQ code indices.
+
+    Buffers (fp32 natural logs): log_pi (S,), log_A (S,S) with log_A[i,j] = log p(z_t=j | z_{t-1}=i),
+    log_B (S,V) with log_B[s,v] = log p(code=v | z=s).  They start random (from `generator`) and
+    row-normalised; -inf entries are structural zeros that EM keeps."""
+
+    def __init__(self, num_states, num_codes, generator=None):
+        super().__init__()
+        S, V = int(num_states), int(num_codes)
+        if not (1 <= S <= MAX_STATES and 1 <= V <= MAX_CODES):
+            raise ValueError(f"CodeHMM: 1 <= num_states <= {MAX_STATES} and 1 <= num_codes <= {MAX_CODES} "
+                             f"(got {S}, {V})")
+        self.num_states, self.num_codes = S, V
+
+        def init(*shape):
+            return _row_log_normalise(torch.rand(*shape, generator=generator, dtype=torch.float64) + 0.5)
+
+        self.register_buffer("log_pi", init(S))
+        self.register_buffer("log_A", init(S, S))
+        self.register_buffer("log_B", init(S, V))
+
+    # ------------------------------------------------------------------ inputs
+    def _inputs(self, codes, lengths):
+        _ext.require_device(self.log_pi, codes)
+        if codes.dim() != 2 or codes.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"CodeHMM: expected codes (B, T) int32 or int64, got {tuple(codes.shape)} {codes.dtype}")
+        codes = codes.to(torch.int32).contiguous()
+        B, T = codes.shape
+        if lengths is None:
+            lengths = torch.full((B,), T, dtype=torch.int64, device=codes.device)
+        lengths = torch.as_tensor(lengths).to(codes.device, torch.int64).contiguous()
+        if lengths.shape != (B,):
+            raise ValueError(f"CodeHMM: lengths must have shape ({B},)")
+        return codes, lengths, B, T
+
+    def _estep(self, codes, lengths, B, T, want_loglik, want_gamma):
+        S, V = self.num_states, self.num_codes
+        dev = codes.device
+        counts = torch.empty(S + S * S + S * V, dtype=torch.float64, device=dev)
+        pi_cnt, trans_cnt, emit_cnt = counts[:S], counts[S:S + S * S].view(S, S), counts[S + S * S:].view(S, V)
+        loglik = torch.empty((B,), dtype=torch.float32, device=dev) if want_loglik else None
+        gamma = torch.empty((B, T, S), dtype=torch.float32, device=dev) if want_gamma else None
+        lib = _ext.load()
+        nb = lib.vqhmm_code_estep_workspace_size(B, T, S, V)
+        ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=dev)
+        with torch.no_grad():
+            _ext.check(lib.vqhmm_code_estep_f32(
+                _ext.ptr(self.log_pi), _ext.ptr(self.log_A), _ext.ptr(self.log_B), _ext.ptr(codes), _ext.ptr(lengths),
+                B, T, S, V, _ext.ptr(pi_cnt), _ext.ptr(trans_cnt), _ext.ptr(emit_cnt), _ext.ptr(loglik),
+                _ext.ptr(gamma), _ext.ptr(ws), nb, _ext.stream_ptr(dev)), "CodeHMM.e_step")
+        out = {"pi_cnt": pi_cnt, "trans_cnt": trans_cnt, "emit_cnt": emit_cnt, "flat": counts}
+        if want_loglik:
+            out["loglik"] = loglik
+        if want_gamma:
+            out["gamma"] = gamma
+        return out
+
+    # ----------------------------------------------------------------- E-step
+    def e_step(self, codes, lengths=None, return_gamma=False):
+        """codes (B,T) int32/int64, lengths (B,) -> dict(pi_cnt (S,), trans_cnt (S,S), emit_cnt (S,V) fp64,
+        loglik (B,) fp32 [, gamma (B,T,S) fp32]); `flat` is the one buffer the three counts are views of
+        (all-reduce it across ranks before m_step for data-parallel EM)."""
+        codes, lengths, B, T = self._inputs(codes, lengths)
+        return self._estep(codes, lengths, B, T, True, return_gamma)
+
+    def log_prob(self, codes, lengths=None):
+        """log p(codes[b, :lengths[b]]) (B,) fp32; NaN for length 0 or a code outside [0, V), -inf if impossible."""
+        codes, lengths, B, T = self._inputs(codes, lengths)
+        return self._estep(codes, lengths, B, T, True, False)["loglik"]
+
+    def posterior(self, codes, lengths=None):
+        """gamma (B,T,S) fp32: p(z_t = s | codes[b, :lengths[b]]), rows at t >= length are 0."""
+        codes, lengths, B, T = self._inputs(codes, lengths)
+        return self._estep(codes, lengths, B, T, False, True)["gamma"]
+
+    # ----------------------------------------------------------------- M-step
+    @staticmethod
+    def _m_rows(cnt, old, prior_count):
+        cnt = cnt.to(torch.float64).reshape(old.shape)
+        live = old != float("-inf")                      # structural zeros stay zeros
+        w = torch.where(live, cnt + prior_count, torch.zeros_like(cnt))
+        tot = w.sum(-1, keepdim=True)
+        new = torch.log(w / tot).float()
+        new = torch.where(live, new, torch.full_like(new, float("-inf")))
+        return torch.where(tot > 0, new, old)            # a row nothing was counted into keeps its parameters
+
+    @torch.no_grad()
+    def m_step(self, counts, prior_count=0.0):
+        """Parameters <- row-normalised (counts + prior_count), in fp64 on the device.  prior_count is added to
+        every count that is not a structural zero; a row whose total is 0 keeps its previous parameters; an
+        -inf parameter stays -inf."""
+        self.log_pi.copy_(self._m_rows(counts["pi_cnt"], self.log_pi, prior_count))
+        self.log_A.copy_(self._m_rows(counts["trans_cnt"], self.log_A, prior_count))
+        self.log_B.copy_(self._m_rows(counts["emit_cnt"], self.log_B, prior_count))
+
+    def fit(self, codes, lengths=None, n_iter=20, tol=None, prior_count=0.0):
+        """Baum-Welch: alternate e_step and m_step.  Returns the total log-likelihoods, one per iteration, each
+        under the parameters before that iteration's M-step (0-dim device tensors with tol=None, so the loop
+        has no host sync; floats with tol, which stops once the improvement per observed position is < tol)."""
+        codes, lengths, B, T = self._inputs(codes, lengths)
+        npos = None
+        history = []
+        for _ in range(int(n_iter)):
+            st = self._estep(codes, lengths, B, T, True, False)
+            total = st["loglik"].double().nansum()
+            self.m_step(st, prior_count)
+            if tol is None:
+                history.append(total)
+                continue
+            if npos is None:
+                npos = max(int(lengths.clamp(0, T).sum().item()), 1)
+            total = float(total.item())
+            if history and (total - history[-1]) / npos < tol:
+                history.append(total)
+                break
+            history.append(total)
+        return history
+
+    # ---------------------------------------------------------------- sampling
+    def sample(self, n, seq_len, generator=None):
+        """Ancestral samples -> (states (n, seq_len), codes (n, seq_len)) int64, drawn by inverse CDF from
+        torch.rand((n, seq_len, 2), generator=generator, device=...).  The code indices are those of the VQ
+        codebook, so `z_q_seq = codebook[codes]` is the `codebook.lookup(z_idx_seq)` of pseudocode.txt:31."""
+        _ext.require_device(self.log_pi)
+        n, seq_len = int(n), int(seq_len)
+        dev = self.log_pi.device
+        u = torch.rand((n, seq_len, 2), generator=generator, device=dev, dtype=torch.float32)
+        states = torch.empty((n, seq_len), dtype=torch.int32, device=dev)
+        codes = torch.empty((n, seq_len), dtype=torch.int32, device=dev)
+        with torch.no_grad():
+            _ext.check(_ext.load().vqhmm_code_sample_f32(
+                _ext.ptr(self.log_pi), _ext.ptr(self.log_A), _ext.ptr(self.log_B), _ext.ptr(u), n, seq_len,
+                self.num_states, self.num_codes, _ext.ptr(states), _ext.ptr(codes), _ext.stream_ptr(dev)),
+                "CodeHMM.sample")
+        return states.long(), codes.long()
