@@ -489,13 +489,10 @@ __global__ __launch_bounds__(512) void strip_fwd_kernel(StripFwdArgs a, HeadArgs
       front_epi(acc, bD, rb, R, T, lg4, l16, slo, shi, a.g1, slot + ST_LDW, nost, -1,
                 wave > 0 ? sh.slot[wave - 1] + 17 * ST_LDW : nullptr, wave < 7 ? sh.slot[wave + 1] : nullptr);
       if (it == 0) stamp<PROF>(11);
-      if (wave == 5 || wave == 6) {
-        const bool lo = wave == 5;
-        f32x4 acc2[4];
-        pk_block(wD, sh.Xq + (lo ? 0 : 16 * 7 + 2) * ST_XLD, a.K, lg4, l16, acc2);
-        front_epi(acc2, bD, lo ? s0 - 1 : s0 + 16 * 7 + 1, R, T, lg4, l16, 0, 0, a.g1,
-                  lo ? sh.slot[0] : sh.slot[7] + 2 * ST_LDW, true, lo ? 0 : 15);
-      }
+      // no blocks for the window's outer g1 rows -1 and 128 (slot 0 row 0, slot 7 row 17), unlike enc_conv1:
+      // they reach only dec_conv2's window rows 0 and 127, which no strip stores (g2 / par go out for rows
+      // ST_HALO .. ST_HALO + ST_OWN - 1 and nothing later reads the slots).  One MFMA column is one row, so
+      // whatever enc_conv1 left in those two slot rows stays inside the discarded rows.
     }
     lds_barrier();  // every slot's rows
     if (it == 0) stamp<PROF>(4);
