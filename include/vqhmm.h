@@ -157,6 +157,40 @@ int vqhmm_fwdbwd_xi_f32(const float* log_pi, const float* log_A, const float* em
                         int64_t B, int64_t T, int64_t K, float* gamma, float* xi, float* logZ,
                         void* workspace, size_t ws_bytes, void* stream);
 
+/* --------------------------------------------------- regime-path samplers ----
+ * N state paths per sequence of the time-varying HMM over the Prior's tables (hmm_sample.hip):
+ *   vqhmm_ffbs_sample_f32    z_{0:L-1} ~ p(z | x_{1:L}) by forward filtering, backward sampling, on
+ *                            filt (B,T,K) as vqhmm_filter_f32 writes it;
+ *   vqhmm_markov_sample_f32  z_0 ~ pi, z_t ~ A_t(z_{t-1}, .): simulation under the tables alone.
+ * 1 <= K <= 32.  log_A (B,T,K,K) with log_A[:, t] the t-1 -> t transition, lengths (B) int64 clamped
+ * to [0, T].  u (B,N,T) fp32 in [0,1): u[b,s,t] is the uniform that draws z_t of sample s.
+ * paths (B,N,T) int32, every element written; -1 at t >= length.  No workspace.
+ *
+ * The draw rule (part of the contract; tests/sample_ref.py restates it).  Given fp32 weights
+ * w_0 .. w_{K-1} >= 0: c_0 = w_0, c_i = c_{i-1} + w_i (a sequential fp32 sum in index order);
+ * thr = u * c_{K-1} (one fp32 product); the draw is the smallest i with c_i > thr, or, if there is
+ * none, the largest i with w_i > 0.  A state of weight 0 is therefore never drawn.  The draw FAILS
+ * when c_{K-1} is 0 or not finite: that position gets -1, and so does every position the walk has
+ * not yet reached in that sample.
+ * The weights are shifted by the max, so a column or row whose entries are all tiny still samples:
+ *   FFBS walks t = L-1 down to 0:  z_{L-1}: w_i = filt[b,L-1,i];  z_{t-1} given j = z_t:
+ *     w_i = filt[b,t-1,i] * expf(log_A[b,t,i,j] - m), m = max_i log_A[b,t,i,j] (m = -inf fails);
+ *   simulation walks t = 0 up to L-1:  z_0: w_i = expf(log_pi[i] - max log_pi);  z_t given
+ *     i = z_{t-1}: w_j = expf(log_A[b,t,i,j] - max_j log_A[b,t,i,j]).
+ * expf is the library function (within 1 ulp), not a fast intrinsic; the product and the sum are
+ * separate roundings (no contraction).
+ * The paths depend only on the inputs and u, never on the grid, the lane mapping or the kernel
+ * variant; two calls give the same bits.  Every global access stays inside its own array (an
+ * exact-size allocation is safe), offsets are 64-bit (B*N*T may pass 2^31).  NaN inputs may yield
+ * any values in {-1, 0 .. K-1}.
+ * Return codes, checked in this order on the host before any launch: a negative size ->
+ * VQHMM_EINVAL; K outside [1, 32] -> VQHMM_EUNSUPPORTED; B*N*T == 0 -> VQHMM_OK without a launch;
+ * a null pointer -> VQHMM_EINVAL.  (T > 2^28 or B >= 2^31: VQHMM_EUNSUPPORTED.) */
+int vqhmm_ffbs_sample_f32(const float* filt, const float* log_A, const int64_t* lengths, const float* u,
+                          int64_t B, int64_t T, int64_t K, int64_t N, int32_t* paths, void* stream);
+int vqhmm_markov_sample_f32(const float* log_pi, const float* log_A, const int64_t* lengths, const float* u,
+                            int64_t B, int64_t T, int64_t K, int64_t N, int32_t* paths, void* stream);
+
 /* ----------------------------------------------- HMM on VQ code indices ----
  * The stationary discrete HMM of the pipeline's second half (pseudocode.txt:25-32: hmm.train_em on
  * the collected code indices, hmm.sample; math.md:23-62 with M_t = M; hmm_code.hip):

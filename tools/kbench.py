@@ -5,6 +5,9 @@
     python tools/kbench.py estep --B 1024 --T 512 --K 8 --V 512 [--old-route]
                                                         (the fused E-step on code indices; --old-route: also
                                                          the same statistics through pairwise_posteriors)
+    python tools/kbench.py sample --B 512 --T 512 --K 8 --N 64
+                                                        (the FFBS and simulation kernels, the filter beside them,
+                                                         and a plain-torch FFBS loop on the same shapes)
 """
 import argparse
 import json
@@ -234,6 +237,80 @@ def bench_estep(a):
         print(json.dumps(rec))
 
 
+def torch_ffbs(filt, log_A, u):
+    """Plain-torch FFBS on full-length sequences, one step per iteration: a gather of the column
+    z_t, a cumsum and a searchsorted (several launches per time step)."""
+    B, T, K = filt.shape
+    N = u.shape[1]
+    paths = torch.empty(B, N, T, dtype=torch.int64, device=filt.device)
+
+    def draw(w, ut):  # w (B, N, K), ut (B, N)
+        c = torch.cumsum(w, dim=2)
+        thr = (ut * c[:, :, -1]).unsqueeze(2)
+        return torch.searchsorted(c, thr, right=True).squeeze(2).clamp_(max=K - 1)
+
+    z = draw(filt[:, T - 1].unsqueeze(1).expand(B, N, K), u[:, :, T - 1])
+    paths[:, :, T - 1] = z
+    for t in range(T - 1, 0, -1):
+        col = torch.gather(log_A[:, t].transpose(1, 2), 1, z.unsqueeze(2).expand(B, N, K))  # log_A_t(:, z_t)
+        w = filt[:, t - 1].unsqueeze(1) * torch.exp(col - col.max(dim=2, keepdim=True).values)
+        z = draw(w, u[:, :, t - 1])
+        paths[:, :, t - 1] = z
+    return paths
+
+
+def bench_sample(a):
+    """vqhmm_ffbs_sample_f32 and vqhmm_markov_sample_f32 at N = --N samples per sequence, the filter
+    (FFBS's forward half) and the plain-torch FFBS loop, alternated after a warm-up (median, min and
+    max of the rounds).  Algorithmic bytes of a sampler: 4 B T (K^2 + K) + 8 B N T (the tables and
+    filt read once, the uniforms read and the paths written)."""
+    B, T, K, N = a.B, a.T, a.K, a.N
+    log_pi, log_A, em, L = hmm_tables(B, T, K)
+    lib = vqhmm._ext.load()
+    P = vqhmm._ext.ptr
+    st = vqhmm._ext.stream_ptr()
+    filt = torch.empty(B, T, K, device="cuda")
+    ll = torch.empty(B, device="cuda")
+    u = torch.rand(B, N, T, device="cuda", generator=torch.Generator(device="cuda").manual_seed(5))
+    pf = torch.empty(B, N, T, dtype=torch.int32, device="cuda")
+    pm = torch.empty(B, N, T, dtype=torch.int32, device="cuda")
+
+    def filt_fn():
+        lib.vqhmm_filter_f32(P(log_pi), P(log_A), P(em), P(L), B, T, K, P(filt), P(ll), st)
+
+    def ffbs():
+        lib.vqhmm_ffbs_sample_f32(P(filt), P(log_A), P(L), P(u), B, T, K, N, P(pf), st)
+
+    def markov():
+        lib.vqhmm_markov_sample_f32(P(log_pi), P(log_A), P(L), P(u), B, T, K, N, P(pm), st)
+
+    filt_fn()
+    ffbs()
+    ref = torch_ffbs(filt, log_A, u)
+    torch.cuda.synchronize()
+    print(json.dumps({"check": "torch loop vs ffbs kernel", "B": B, "T": T, "K": K, "N": N,
+                      "rows_differing": int((ref != pf.long()).any(dim=2).sum()), "rows": B * N}))
+    legs = {"filter": filt_fn, "ffbs_sample": ffbs, "markov_sample": markov,
+            "torch_ffbs_loop": lambda: torch_ffbs(filt, log_A, u)}
+    iters = {"filter": 10, "ffbs_sample": 10, "markov_sample": 10, "torch_ffbs_loop": 1}
+    for k, fn in legs.items():
+        time_fn(fn, iters=2 if k != "torch_ffbs_loop" else 1, warmup=2 if k != "torch_ffbs_loop" else 1)
+    rounds = {k: [] for k in legs}
+    for _ in range(7):
+        for k, fn in legs.items():
+            rounds[k].append(time_fn(fn, iters=iters[k], warmup=1 if k != "torch_ffbs_loop" else 0))
+    t = {k: sorted(v)[len(v) // 2] for k, v in rounds.items()}
+    byts = 4 * B * T * (K * K + K) + 8 * B * N * T
+    for k in legs:
+        rec = {"kernel": k, "B": B, "T": T, "K": K, "N": N, "us": t[k] * 1e6, "min_us": min(rounds[k]) * 1e6,
+               "max_us": max(rounds[k]) * 1e6}
+        if k.endswith("_sample"):
+            rec.update({"GBps": byts / t[k] / 1e9, "frac_hbm": byts / t[k] / HBM_PEAK, "x_filter": t[k] / t["filter"]})
+        if k == "torch_ffbs_loop":
+            rec["x_ffbs_sample"] = t[k] / t["ffbs_sample"]
+        print(json.dumps(rec))
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("what")
@@ -242,7 +319,9 @@ if __name__ == "__main__":
     ap.add_argument("--T", type=int, default=200)
     ap.add_argument("--K", type=int, default=32)
     ap.add_argument("--V", type=int, default=512)
+    ap.add_argument("--N", type=int, default=64)
     ap.add_argument("--old-route", action="store_true")
     a = ap.parse_args()
     {"vq": bench_vq, "stream": bench_stream, "viterbi": bench_viterbi, "fwdbwd": bench_fwdbwd,
-     "filter": bench_filter, "xi": bench_xi, "estep": bench_estep}[a.what](a)
+     "filter": bench_filter, "xi": bench_xi, "estep": bench_estep,
+     "sample": bench_sample}[a.what](a)

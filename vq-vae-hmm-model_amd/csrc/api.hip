@@ -410,6 +410,24 @@ int vqhmm_code_sample_f32(const float* log_pi, const float* log_A, const float* 
   return launch_hmm_code_sample(log_pi, log_A, log_B, uniforms, N, T, S, V, states, codes, (hipStream_t)stream);
 }
 
+int vqhmm_ffbs_sample_f32(const float* filt, const float* log_A, const int64_t* lengths, const float* u, int64_t B,
+                          int64_t T, int64_t K, int64_t N, int32_t* paths, void* stream) {
+  if (B < 0 || T < 0 || K < 0 || N < 0) return VQHMM_EINVAL;
+  if (K < 1 || K > 32) return VQHMM_EUNSUPPORTED;
+  if (B == 0 || N == 0 || T == 0) return VQHMM_OK;
+  if (!filt || !log_A || !lengths || !u || !paths) return VQHMM_EINVAL;
+  return launch_hmm_ffbs_sample(filt, log_A, lengths, u, B, T, K, N, paths, (hipStream_t)stream);
+}
+
+int vqhmm_markov_sample_f32(const float* log_pi, const float* log_A, const int64_t* lengths, const float* u,
+                            int64_t B, int64_t T, int64_t K, int64_t N, int32_t* paths, void* stream) {
+  if (B < 0 || T < 0 || K < 0 || N < 0) return VQHMM_EINVAL;
+  if (K < 1 || K > 32) return VQHMM_EUNSUPPORTED;
+  if (B == 0 || N == 0 || T == 0) return VQHMM_OK;
+  if (!log_pi || !log_A || !lengths || !u || !paths) return VQHMM_EINVAL;
+  return launch_hmm_markov_sample(log_pi, log_A, lengths, u, B, T, K, N, paths, (hipStream_t)stream);
+}
+
 int vqhmm_elbo_workspace_size(const vqhmm_dims_t* d, int64_t B, int64_t T, size_t* bytes) {
   if (!dims_ok(d) || B < 0 || T < 0 || !bytes) return VQHMM_EINVAL;
   *bytes = plan_elbo(d, B, T, nullptr).bytes;

@@ -501,6 +501,12 @@ int launch_hmm_filter(const float* log_pi, const float* log_A, const float* em, 
                       int64_t T, int64_t K, float* filt, float* loglik, hipStream_t s);
 int launch_hmm_xi(const float* log_A, const float* filt, const float* gamma, const int64_t* lengths, int64_t B,
                   int64_t T, int64_t K, float* xi, hipStream_t s);
+// regime-path samplers over the Prior's tables, 1 <= K <= 32 (hmm_sample.hip): backward sampling on the
+// filter's filt, and the forward walk from log_pi; u (B,N,T) uniforms, paths (B,N,T)
+int launch_hmm_ffbs_sample(const float* filt, const float* log_A, const int64_t* lengths, const float* u, int64_t B,
+                           int64_t T, int64_t K, int64_t N, int32_t* paths, hipStream_t s);
+int launch_hmm_markov_sample(const float* log_pi, const float* log_A, const int64_t* lengths, const float* u,
+                             int64_t B, int64_t T, int64_t K, int64_t N, int32_t* paths, hipStream_t s);
 // stationary HMM on code indices, 1 <= S <= 32, 1 <= V <= 65536 (hmm_code.hip): the fused E-step (counts in
 // fp64, loglik and gamma nullable; ws = hmm_code_estep_ws_bytes) and the inverse-CDF ancestral sampler
 bool hmm_code_supported(int64_t S, int64_t V);

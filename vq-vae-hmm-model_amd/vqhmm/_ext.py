@@ -50,6 +50,8 @@ _SIGS = {
     "vqhmm_fwdbwd_xi_workspace_size": (c_sz, [c_i64, c_i64, c_i64]),
     "vqhmm_fwdbwd_xi_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_sz,
                                            c_vp]),
+    "vqhmm_ffbs_sample_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp]),
+    "vqhmm_markov_sample_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp]),
     "vqhmm_code_estep_workspace_size": (c_sz, [c_i64, c_i64, c_i64, c_i64]),
     "vqhmm_code_estep_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp,
                                             c_vp, c_vp, c_vp, c_sz, c_vp]),

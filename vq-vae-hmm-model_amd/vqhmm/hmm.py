@@ -231,6 +231,86 @@ def forward_filter(log_pi, log_A, em, lengths=None):
     return filt, loglik
 
 
+def _sample_uniforms(uniforms, B, N, T, device, generator, what):
+    if uniforms is None:
+        return torch.rand((B, N, T), generator=generator, device=device, dtype=torch.float32)
+    _ext.require_device(uniforms)
+    if tuple(uniforms.shape) != (B, N, T) or uniforms.dtype != torch.float32:
+        raise ValueError(f"{what}: uniforms must be fp32 of shape ({B}, {N}, {T}), got {uniforms.dtype} "
+                         f"{tuple(uniforms.shape)}")
+    return uniforms.detach().contiguous()
+
+
+def _n_samples(n_samples, what):
+    n = int(n_samples)
+    if n < 0:
+        raise ValueError(f"{what}: n_samples must be >= 0 (got {n_samples})")
+    return n
+
+
+def sample_posterior_paths(log_pi, log_A, em, lengths=None, n_samples=1, generator=None, uniforms=None):
+    """n_samples regime paths per sequence from the posterior p(z_{0:L-1} | x_{1:L}) by forward
+    filtering, backward sampling: vqhmm_filter_f32, then vqhmm_ffbs_sample_f32 on its filt.
+
+    Inputs as forward_filter's (1 <= K <= 32).  Returns paths (B, n_samples, T) int32, -1 past each
+    length.  A sequence whose log-likelihood is not finite (impossible under the tables, or of
+    length 0) has no posterior: all of its samples are -1, its batch neighbours are unaffected.
+    uniforms: a (B, n_samples, T) fp32 device tensor in [0, 1), used as it is; uniforms[b, s, t]
+    draws z_t of sample s by the inverse-CDF rule of include/vqhmm.h, so the same uniforms give the
+    same paths (reproducible draws, common random numbers across scenarios).  Without it the
+    function draws torch.rand((B, n_samples, T), generator=generator) on the device; either way that
+    buffer costs 4 * B * n_samples * T bytes.  Runs under no_grad on detached inputs."""
+    log_pi, log_A, em, lengths, B, T, K = _hmm_inputs(log_pi, log_A, em, lengths)
+    N = _n_samples(n_samples, "sample_posterior_paths")
+    if K > PAIR_MAX_K:
+        raise RuntimeError(f"sample_posterior_paths: K <= {PAIR_MAX_K} states (got K = {K})")
+    with torch.no_grad():
+        if B * N * T == 0:
+            return torch.full((B, N, T), -1, dtype=torch.int32, device=em.device)
+        paths = torch.empty((B, N, T), dtype=torch.int32, device=em.device)  # the kernel writes every element
+        u = _sample_uniforms(uniforms, B, N, T, em.device, generator, "sample_posterior_paths")
+        log_pi, log_A, em = log_pi.detach(), log_A.detach(), em.detach()
+        filt = torch.empty((B, T, K), dtype=torch.float32, device=em.device)
+        loglik = torch.empty((B,), dtype=torch.float32, device=em.device)
+        lib = _ext.load()
+        st = _ext.stream_ptr(em.device)
+        _ext.check(lib.vqhmm_filter_f32(_ext.ptr(log_pi), _ext.ptr(log_A), _ext.ptr(em), _ext.ptr(lengths), B, T, K,
+                                        _ext.ptr(filt), _ext.ptr(loglik), st), "sample_posterior_paths (filter)")
+        _ext.check(lib.vqhmm_ffbs_sample_f32(_ext.ptr(filt), _ext.ptr(log_A), _ext.ptr(lengths), _ext.ptr(u), B, T, K,
+                                             N, _ext.ptr(paths), st), "sample_posterior_paths")
+        return torch.where(torch.isfinite(loglik)[:, None, None], paths, torch.full_like(paths, -1))
+
+
+def simulate_paths(log_pi, log_A, lengths=None, n_samples=1, generator=None, uniforms=None):
+    """n_samples regime paths per sequence simulated under the tables alone: z_0 ~ softmax(log_pi),
+    z_t ~ softmax_j(log_A[b, t, z_{t-1}, :]) (vqhmm_markov_sample_f32); no observations enter.
+
+    log_pi (K,), log_A (B,T,K,K) as Prior.forward returns them (1 <= K <= 32; rows need not be
+    normalised, -inf is a structural zero that is never drawn).  Returns paths (B, n_samples, T)
+    int32, -1 past each length (and from the first position whose row has no mass onward).
+    uniforms / generator: as sample_posterior_paths; the (B, n_samples, T) fp32 buffer costs
+    4 * B * n_samples * T bytes.  Runs under no_grad on detached inputs."""
+    _ext.require_device(log_pi, log_A)
+    if log_A.dim() != 4 or log_A.shape[2] != log_A.shape[3]:
+        raise ValueError(f"expected log_A (B,T,K,K), got {tuple(log_A.shape)}")
+    B, T, K = log_A.shape[:3]
+    em = log_A.new_empty((B, T, K))  # shape carrier for the shared validation, never read
+    log_pi, log_A, _, lengths, B, T, K = _hmm_inputs(log_pi, log_A, em, lengths)
+    N = _n_samples(n_samples, "simulate_paths")
+    if K > PAIR_MAX_K:
+        raise RuntimeError(f"simulate_paths: K <= {PAIR_MAX_K} states (got K = {K})")
+    with torch.no_grad():
+        if B * N * T == 0:
+            return torch.full((B, N, T), -1, dtype=torch.int32, device=log_A.device)
+        paths = torch.empty((B, N, T), dtype=torch.int32, device=log_A.device)  # the kernel writes every element
+        u = _sample_uniforms(uniforms, B, N, T, log_A.device, generator, "simulate_paths")
+        log_pi, log_A = log_pi.detach(), log_A.detach()
+        _ext.check(_ext.load().vqhmm_markov_sample_f32(_ext.ptr(log_pi), _ext.ptr(log_A), _ext.ptr(lengths),
+                                                       _ext.ptr(u), B, T, K, N, _ext.ptr(paths),
+                                                       _ext.stream_ptr(log_A.device)), "simulate_paths")
+        return paths
+
+
 def pairwise_posteriors(log_pi, log_A, em, lengths=None):
     """gamma (B,T,K), xi (B,T,K,K), logZ (B,): xi[b,t,i,j] = p(z_{t-1} = i, z_t = j | x_{1:L}) for
     1 <= t < L and 0 elsewhere (the E-step statistics of EM on the transition model: sum_t xi_t);

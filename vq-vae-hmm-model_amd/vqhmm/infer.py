@@ -11,6 +11,10 @@
                             posterior as emission (log_softmax(logits)).
   filtered_regimes(...)     causal regime probabilities p(z_t | x_{1:t}) and their argmax under the
                             same tables and emissions (vqhmm_filter_f32): no look-ahead.
+  sampled_regimes(...)      regime paths drawn from the posterior under the same tables and emissions (forward
+                            filtering, backward sampling: vqhmm_filter_f32 + vqhmm_ffbs_sample_f32).
+  simulate_regimes(...)     regime paths simulated forward under Prior(u) alone (vqhmm_markov_sample_f32): the
+                            learned, input-conditioned replacement of a back-test's hard-coded switching chain.
   prior_viterbi(...)        Viterbi over Prior.forward's tables computed on the chip from u
                             (SURVEY §8f-3, vqhmm_prior_viterbi_f32): log_A never touches HBM;
                             bit-identical to viterbi(*model.prior(u), em).
@@ -20,7 +24,7 @@ import ctypes
 import torch
 
 from . import _ext
-from .hmm import forward_filter, regime_argmax, viterbi
+from .hmm import forward_filter, regime_argmax, sample_posterior_paths, simulate_paths, viterbi
 
 
 def _device(model):
@@ -139,3 +143,25 @@ def viterbi_regimes(model, x, u, lengths=None, fused=True):
                 return r
         log_pi, log_A = model.prior(u)
         return viterbi(log_pi, log_A, em, lengths)
+
+
+def sampled_regimes(model, x, u, lengths=None, n_samples=1, generator=None, uniforms=None):
+    """n_samples regime paths per sequence from p(z_{0:L-1} | x) under the Prior's tables with the
+    encoder posterior as emission (em = log_softmax(logits), as viterbi_regimes forms it):
+    (B, n_samples, T) int32, -1 past each length.  Where viterbi_regimes gives the one MAP path, these
+    carry the uncertainty over whole paths (regime durations, the chance of a switch inside a window).
+    generator / uniforms: as sample_posterior_paths."""
+    with torch.no_grad():
+        em = torch.log_softmax(model.encode(x), dim=1).transpose(1, 2).contiguous()
+        log_pi, log_A = model.prior(u)
+        return sample_posterior_paths(log_pi, log_A, em, lengths, n_samples, generator, uniforms)
+
+
+def simulate_regimes(model, u, lengths=None, n_samples=1, generator=None, uniforms=None):
+    """n_samples regime paths per sequence simulated forward under model.prior(u) alone (no
+    observations): (B, n_samples, T) int32, -1 past each length.  The scenario generator of a Monte
+    Carlo back-test on the learned, input-conditioned transitions.  generator / uniforms: as
+    simulate_paths."""
+    with torch.no_grad():
+        log_pi, log_A = model.prior(u)
+        return simulate_paths(log_pi, log_A, lengths, n_samples, generator, uniforms)
