@@ -8,7 +8,8 @@
 // of every dY and X) is gone.
 //
 // dW[o][c][tap] = sum_r dY[r][o] X[r + tap - 1][c] over owned rows r: dY of every layer is exact on the owned
-// rows (the chain's inexact halo rows are the window's outer two), and X comes from HBM (exact anywhere).
+// rows (the chain's inexact halo rows are the window's first three and last three: SW_LO, SW_OWN below), and X comes from
+// HBM (exact anywhere).
 // One MFMA per 16 x 16 tile per 4 rows (K = rows); the 86 tiles of the six layers are split over the 8 waves
 // (11 / 10 per wave, 44 accumulator registers), so each wave runs its tiles over ALL owned rows and every
 // operand is read from a window-wide LDS buffer: dY where the chain already keeps it (dg2 in the slots, dg1,
@@ -42,6 +43,14 @@ __device__ float g_bwdw_one = 1.0f;  // the scale behind a null scale pointer
 namespace {
 constexpr int SW_LDD = 24;  // dpar rows in LDS (ldp <= 16 channels; 2 * 24 = 16 mod 32: conflict-free column reads)
 constexpr int SW_LDQ = 8;   // q / x / dlog rows in LDS
+// The folded strip's halo is asymmetric: the owned rows start at window row SW_LO = 3 and a strip owns at most
+// SW_OWN = 120 rows.  The 1x1 front gives dg2 on window rows 0..127 only, so dg1 is exact on rows 1..126, dh2 and
+// dlog on 2..125 and dh1 on 3..124: every owned row 3..122 and the weight gradients' dY operands are exact with no
+// front block for rows -1 and 128.  (Wave 0's slot row 0 and wave 7's slot row 17 are never written; one MFMA
+// column is one row, so what they hold reaches only the non-owned rows 0..2 and 125..127.)
+constexpr int SW_LO = 3;
+constexpr int SW_OWN = 120;
+static_assert(SW_OWN % 4 == 0 && SW_LO + SW_OWN - 1 <= ST_WIN - 4, "dh1 is exact on window rows 3 .. ST_WIN - 4");
 
 struct StripWLds {
   float RW[3 * 64 * ST_LDW];        // 13824
@@ -225,7 +234,7 @@ __global__ __launch_bounds__(512) void strip_bwdw_kernel(SWArgs a, ConvArgs f) {
   const int lg4 = lane >> 4, l16 = lane & 15;
   const int64_t R = a.R;
   const int T = a.T, own = a.own, nstep = own / 4;
-  constexpr int lo = ST_HALO;  // first owned window row
+  constexpr int lo = SW_LO;  // first owned window row
   float* slot = sh.RS + wave * 18 * ST_LDW;
   if (a.step_inc && blockIdx.x == 0 && tid == 0) *a.step_inc = (*a.step_inc & 0xffffffffll) + 1;
 
@@ -348,7 +357,10 @@ __global__ __launch_bounds__(512) void strip_bwdw_kernel(SWArgs a, ConvArgs f) {
     // being hoisted out of the loop as 64-bit VGPR pairs (the accumulators need those registers)
     int tidv = tid;
     asm volatile("" : "+v"(tidv));
-    if (it == a.prof_it) stamp<PROF>(15);  // the profiled strip's start (VQHMM_STRIP_PROF_IT)
+    // the profiled strip's start (VQHMM_STRIP_PROF_IT): the clock is read here and stored after B1.  Stored here,
+    // the stamp sat in front of the loop header's vmcnt(0) and P1's loads were issued only after its round trip
+    [[maybe_unused]] unsigned long long t15 = 0;
+    if constexpr (PROF > 0) { if (it == a.prof_it) t15 = __builtin_amdgcn_s_memrealtime(); }
     // the device scalars, per strip (L2-hot after the first), as VECTOR loads (opaque zero index) issued ahead
     // of P1's loads: waited with them.  Loaded once before the loop they cost the first strip a vmcnt(0)
     // (a register copy of the value) that also waited for the compact image's DMA
@@ -363,7 +375,7 @@ __global__ __launch_bounds__(512) void strip_bwdw_kernel(SWArgs a, ConvArgs f) {
     const bool qok = l16 < 3 * K;
     const int xtap = l16 / D, xc = l16 - xtap * D;
     const bool xok = l16 < 3 * D;
-    const int64_t s0 = s * own - ST_HALO;  // PCL row of window row 0
+    const int64_t s0 = s * own - SW_LO;  // PCL row of window row 0
     const int64_t rb = s0 + 16 * wave;
     // dpar row r, channels 4 lg4 ..: the raw load from a clamped address, and its mask (rows outside / pad
     // channels 0) applied where it is used, so no wait sits right behind the load
@@ -393,15 +405,11 @@ __global__ __launch_bounds__(512) void strip_bwdw_kernel(SWArgs a, ConvArgs f) {
 #pragma unroll
           for (int nb = 0; nb < 4; ++nb) acc[nb] = mfma16x16x4(wP[nb][e], b[e], acc[nb]);
       };
-      const bool extra = wave == 5 || wave == 6;
-      const int64_t re = wave == 5 ? s0 - 1 : s0 + 16 * 7 + 1;
-      // every load of this phase unconditional (clamped addresses; only the waves that need a value use it):
-      // a branch join before the image DMA below would make the compiler drain vmcnt before the front
-      float4 mA[4], xA, mB[4], xB;
+      // every load of this phase unconditional (clamped addresses): a branch join before the image DMA below
+      // would make the compiler drain vmcnt before the front
+      float4 mA[4], xA;
       load_mask(a.g2, rb, R, lg4, l16, mA);
       xA = ld_dpar_raw(rb + l16);
-      load_mask(a.g2, re, R, lg4, l16, mB);  // waves 5 and 6: the window's outer rows
-      xB = ld_dpar_raw(re + l16);
       float4 qv;
       {
         int64_t r = s0 + (tidv & (ST_WIN - 1));
@@ -420,12 +428,6 @@ __global__ __launch_bounds__(512) void strip_bwdw_kernel(SWArgs a, ConvArgs f) {
       }
       mask_epi(acc, mA, psc, rb, R, T, lg4, l16, slo, shi, a.store ? a.dg2 : nullptr, slot + ST_LDW, ST_LDW, -1,
                wave > 0 ? slot - 18 * ST_LDW + 17 * ST_LDW : nullptr, wave < 7 ? slot + 18 * ST_LDW : nullptr);
-      if (extra) {
-        f32x4 acc2[4];
-        front(dpar_mask(re + l16, xB), acc2);
-        mask_epi(acc2, mB, psc, re, R, T, lg4, l16, 0, 0, nullptr,
-                 wave == 5 ? sh.RS : sh.RS + 7 * 18 * ST_LDW + 2 * ST_LDW, ST_LDW, wave == 5 ? 0 : 15);
-      }
 #pragma unroll
       for (int nb = 0; nb < 4; ++nb)
         *reinterpret_cast<float4*>(sh.RG + (16 * wave + l16) * ST_LDW + nb * 16 + 4 * lg4) = m1[nb];
@@ -438,6 +440,7 @@ __global__ __launch_bounds__(512) void strip_bwdw_kernel(SWArgs a, ConvArgs f) {
     asm volatile("s_waitcnt vmcnt(7)" ::: "memory");  // (P1's loads: already consumed)
     lds_barrier_dma();  // B1: slots, G1, Q
     if (it == a.prof_it) stamp<PROF>(1);
+    if constexpr (PROF > 0) { if (it == a.prof_it && tid == 0 && blockIdx.x < 256) g_prof[blockIdx.x * 16 + 15] = t15; }
     // ================= P2: dec_conv2 weight gradient (needs no image: hides the first strip's image DMA), then
     // dec_conv2 dgrad (mask g1) -> dg1 (registers)
     f32x4 mA[4];  // g2 / dpar rows again (L2), for G2 / DP in P3: in flight across this phase
@@ -678,12 +681,12 @@ bool strip_bwdw_supported(const ConvArgs& pd, const ConvArgs& d2, const ConvArgs
          3 * f.N <= 16;
 }
 
-// owned rows per strip: a multiple of 4 (the MFMA steps), at most ST_OWN, sized so that the strips cover the
-// rows in as few rounds of 256 workgroups as ST_OWN allows with every workgroup busy in the last one
+// owned rows per strip: a multiple of 4 (the MFMA steps), at most SW_OWN, sized so that the strips cover the
+// rows in as few rounds of 256 workgroups as SW_OWN allows with every workgroup busy in the last one
 int strip_bwdw_own(int64_t R) {
-  const int64_t rounds = cdiv(R, 256ll * ST_OWN);
+  const int64_t rounds = cdiv(R, 256ll * SW_OWN);
   const int64_t own = cdiv(cdiv(R, 256 * rounds), 4) * 4;
-  return (int)(own < 4 ? 4 : own > ST_OWN ? ST_OWN : own);
+  return (int)(own < 4 ? 4 : own > SW_OWN ? SW_OWN : own);
 }
 
 int strip_bwdw_grid(int64_t R) {
