@@ -227,7 +227,59 @@ int vqhmm_markov_sample_f32(const float* log_pi, const float* log_A, const int64
  * row z_{t-1} of A afterwards), uniforms[n,t,1] draws the code from row z_t of B.  The rule is part
  * of the contract: p_k = exp(log p_k) in fp32, cdf_k = the fp32 running sum in index order divided
  * by its own total, the draw is the first k with u < cdf_k, or the last k with p_k > 0 if there is
- * none; a zero-probability category is never drawn.  states (N,T), codes (N,T) int32.  No workspace. */
+ * none; a zero-probability category is never drawn.  states (N,T), codes (N,T) int32.  No workspace.
+ *
+ * vqhmm_code_viterbi_f32 and vqhmm_code_filter_f32 (hmm_code_decode.hip): the MAP state path and the
+ * causal filter of a code sequence, read from the 4-byte codes alone: no (B,T,S,S) / (B,T,S) table
+ * is ever built, the transition matrix stays in registers for the whole sequence and the emission
+ * table in LDS (read through L2 when S*V*4 > 64 KB).  Parameters, codes, lengths and the S, V limits
+ * as above.
+ *
+ * vqhmm_code_viterbi_f32: path (B,T) int32, score (B) fp32.
+ *   d_0[j] = log_pi[j] + log_B[j,c_0],  d_t[j] = (max_i (d_{t-1}[i] + log_A[i,j])) + log_B[j,c_t]
+ * in fp32 in exactly this order, i ascending with a strict > (ties keep the lowest i); the last state
+ * is the first argmax of d_{L-1}, score = d_{L-1}[last]; path[t >= L] = -1 and every element of path
+ * is written.  L = 0: path all -1, score = -inf.  A code outside [0, V) inside the length: path all
+ * -1, score = NaN, the other sequences untouched.  An impossible sequence gets what the rule gives:
+ * score = -inf and the path of the tie rule.  For every sequence with valid codes the result is
+ * bit-identical to vqhmm_viterbi_f32 on log_A[b,t] = log_A, em[b,t,j] = log_B[j, codes[b,t]].
+ * Workspace: vqhmm_code_viterbi_workspace_size(B, T, S, V) bytes: one backpointer byte per step and
+ * state (B * 4*ceil(T/4) * SP, SP = S rounded up to a power of two) and the (V,S) log_B^T table.
+ *
+ * vqhmm_code_filter_f32: filt (B,T,S) fp32 with filt[b,t,j] = p(z_t = j | codes_{b,0:t}) (rows
+ * t < L sum to 1, rows t >= L are 0, every element written), last (B,S) = filt[b, L_b - 1] and
+ * loglik (B) = log p(codes_{b,0:L_b} | prev); each of the three is nullable, and with filt NULL nothing
+ * of size B*T*S is written (the streaming / scoring form).  prev (B,S), nullable, is the filtered
+ * distribution at the position just before this chunk (non-negative, need not be normalised): the
+ * distribution before the emission at t = 0 is exp(log_pi) with prev NULL and prev[b] . exp(log_A)
+ * otherwise (log_pi is then not read and may be NULL), so feeding a call's last as the next call's prev
+ * filters a feed chunk by chunk; last may alias prev.  L_b = 0: last[b] = prev[b] (zeros without
+ * prev), loglik = NaN.  An impossible sequence (mass truly 0, or sum(prev[b]) = 0) gets loglik = -inf,
+ * a code outside [0, V) inside the length loglik = NaN; in both cases the rows of filt from the
+ * failing position on, and last, are 0, and the other sequences are untouched.  Numerics are the
+ * E-step's forward (normalised every step, step masses' logs summed in fp64, max-shifted natural-log
+ * step when a mass leaves [2^-30, 2^30]).  Workspace: vqhmm_code_filter_workspace_size(B, T, S, V)
+ * bytes (the emission table).  Accuracy target vs the fp64 oracle: |filt|, |last| abs 1e-5, loglik
+ * rel 1e-5 of max(1, |loglik|).
+ *
+ * Both: deterministic, graph-capturable, no host sync, 64-bit offsets, every global access inside
+ * its own array (exact-size allocations and pointers misaligned by 4 bytes are safe).  Return
+ * codes, checked in this order on the host before any launch: a negative size -> VQHMM_EINVAL; S or
+ * V out of range -> VQHMM_EUNSUPPORTED; B > 0, T = 0 -> as if every length were 0 (the size-B outputs
+ * are written); B = 0 -> VQHMM_OK; a null required pointer or a workspace that is too small ->
+ * VQHMM_EINVAL. */
+size_t vqhmm_code_viterbi_workspace_size(int64_t B, int64_t T, int64_t S, int64_t V);
+int vqhmm_code_viterbi_f32(const float* log_pi, const float* log_A, const float* log_B,
+                           const int32_t* codes, const int64_t* lengths,
+                           int64_t B, int64_t T, int64_t S, int64_t V,
+                           int32_t* path, float* score,
+                           void* workspace, size_t ws_bytes, void* stream);
+size_t vqhmm_code_filter_workspace_size(int64_t B, int64_t T, int64_t S, int64_t V);
+int vqhmm_code_filter_f32(const float* log_pi, const float* log_A, const float* log_B,
+                          const int32_t* codes, const int64_t* lengths, const float* prev,
+                          int64_t B, int64_t T, int64_t S, int64_t V,
+                          float* filt, float* last, float* loglik,
+                          void* workspace, size_t ws_bytes, void* stream);
 size_t vqhmm_code_estep_workspace_size(int64_t B, int64_t T, int64_t S, int64_t V);
 int vqhmm_code_estep_f32(const float* log_pi, const float* log_A, const float* log_B,
                          const int32_t* codes, const int64_t* lengths,

@@ -5,6 +5,10 @@
     python tools/kbench.py estep --B 1024 --T 512 --K 8 --V 512 [--old-route]
                                                         (the fused E-step on code indices; --old-route: also
                                                          the same statistics through pairwise_posteriors)
+    python tools/kbench.py code_viterbi --B 512 --T 512 --K 8 --V 512 [--old-route]
+    python tools/kbench.py code_filter --B 2048 --T 200 --K 32 --V 512 [--old-route]
+                                                        (CodeHMM's fused decode / causal filter; --old-route: also
+                                                         the expanded tables through viterbi / forward_filter)
     python tools/kbench.py sample --B 512 --T 512 --K 8 --N 64
                                                         (the FFBS and simulation kernels, the filter beside them,
                                                          and a plain-torch FFBS loop on the same shapes)
@@ -237,6 +241,90 @@ def bench_estep(a):
         print(json.dumps(rec))
 
 
+def _bench_code_decode(a, leg):
+    """One of CodeHMM's fused read-outs at S = --K states, V = --V codes on full-length sequences.  --old-route:
+    also the time-varying entry point's way to the same result (log_A broadcast to (B,T,S,S), the log_B[:, codes]
+    gather to (B,T,S), then viterbi / forward_filter; building the tables is part of its time), in five
+    alternating pairs after a warm-up, every pair's two times reported, and a line that checks the two routes
+    agree.  Algorithmic HBM bytes per position: the code read (4) and the path (4) or filt (4 S) written; the
+    old route's: 4 S^2 + 4 S written, then read, plus the same output."""
+    B, T, S, V = a.B, a.T, a.K, a.V
+    g = torch.Generator(device="cuda").manual_seed(11)
+    hmm = vqhmm.CodeHMM(S, V, generator=torch.Generator().manual_seed(3)).cuda()
+    codes = torch.randint(0, V, (B, T), device="cuda", generator=g, dtype=torch.int32)
+    L = torch.full((B,), T, dtype=torch.int64, device="cuda")
+    lib = vqhmm._ext.load()
+    P = vqhmm._ext.ptr
+    st = vqhmm._ext.stream_ptr()
+    cl = codes.long()
+    if leg == "code_viterbi":
+        path = torch.empty(B, T, dtype=torch.int32, device="cuda")
+        score = torch.empty(B, device="cuda")
+        nb = lib.vqhmm_code_viterbi_workspace_size(B, T, S, V)
+        ws = torch.empty(max(nb, 1), dtype=torch.uint8, device="cuda")
+
+        def new():
+            lib.vqhmm_code_viterbi_f32(P(hmm.log_pi), P(hmm.log_A), P(hmm.log_B), P(codes), P(L), B, T, S, V, P(path),
+                                       P(score), P(ws), nb, st)
+
+        def old():
+            return vqhmm.viterbi(hmm.log_pi, hmm.log_A.expand(B, T, S, S), hmm.log_B[:, cl].permute(1, 2, 0), L)
+
+        out_bytes = 4
+    else:
+        filt = torch.empty(B, T, S, device="cuda")
+        last = torch.empty(B, S, device="cuda")
+        ll = torch.empty(B, device="cuda")
+        nb = lib.vqhmm_code_filter_workspace_size(B, T, S, V)
+        ws = torch.empty(max(nb, 1), dtype=torch.uint8, device="cuda")
+
+        def new():
+            lib.vqhmm_code_filter_f32(P(hmm.log_pi), P(hmm.log_A), P(hmm.log_B), P(codes), P(L), None, B, T, S, V,
+                                      P(filt), P(last), P(ll), P(ws), nb, st)
+
+        def old():
+            return vqhmm.forward_filter(hmm.log_pi, hmm.log_A.expand(B, T, S, S), hmm.log_B[:, cl].permute(1, 2, 0), L)
+
+        out_bytes = 4 * S
+    legs = {leg: new}
+    if a.old_route:
+        legs["old_route"] = old
+        ref = old()
+        new()
+        torch.cuda.synchronize()
+        if leg == "code_viterbi":
+            chk = {"paths_equal": bool(torch.equal(ref[0], path)),
+                   "scores_equal": bool(torch.equal(ref[1].view(torch.int32), score.view(torch.int32)))}
+        else:
+            chk = {"filt_maxdiff": (ref[0] - filt).abs().max().item(),
+                   "loglik_max_rel": ((ref[1] - ll).abs() / ll.abs().clamp(min=1)).max().item()}
+        print(json.dumps({"check": "old_route vs " + leg, "B": B, "T": T, "S": S, "V": V, **chk}))
+    for fn in legs.values():
+        time_fn(fn, iters=3, warmup=2)
+    rounds = {k: [] for k in legs}
+    for _ in range(5):
+        for k, fn in legs.items():
+            rounds[k].append(time_fn(fn, iters=10, warmup=1))
+    t = {k: sorted(v)[len(v) // 2] for k, v in rounds.items()}
+    n = B * T
+    byts = {leg: n * (4 + out_bytes), "old_route": n * (2 * (4 * S * S + 4 * S) + 4 + out_bytes)}
+    for k in legs:
+        rec = {"kernel": k, "B": B, "T": T, "S": S, "V": V, "us": t[k] * 1e6, "pairs_us": [r * 1e6 for r in rounds[k]],
+               "GBps": byts[k] / t[k] / 1e9, "frac_hbm": byts[k] / t[k] / HBM_PEAK}
+        if k == "old_route":
+            rec["x_" + leg] = t[k] / t[leg]
+            rec["fused_faster_in_every_pair"] = all(o > f for o, f in zip(rounds[k], rounds[leg]))
+        print(json.dumps(rec))
+
+
+def bench_code_viterbi(a):
+    _bench_code_decode(a, "code_viterbi")
+
+
+def bench_code_filter(a):
+    _bench_code_decode(a, "code_filter")
+
+
 def torch_ffbs(filt, log_A, u):
     """Plain-torch FFBS on full-length sequences, one step per iteration: a gather of the column
     z_t, a cumsum and a searchsorted (several launches per time step)."""
@@ -323,5 +411,5 @@ if __name__ == "__main__":
     ap.add_argument("--old-route", action="store_true")
     a = ap.parse_args()
     {"vq": bench_vq, "stream": bench_stream, "viterbi": bench_viterbi, "fwdbwd": bench_fwdbwd,
-     "filter": bench_filter, "xi": bench_xi, "estep": bench_estep,
-     "sample": bench_sample}[a.what](a)
+     "filter": bench_filter, "xi": bench_xi, "estep": bench_estep, "code_viterbi": bench_code_viterbi,
+     "code_filter": bench_code_filter, "sample": bench_sample}[a.what](a)

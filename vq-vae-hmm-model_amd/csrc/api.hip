@@ -410,6 +410,40 @@ int vqhmm_code_sample_f32(const float* log_pi, const float* log_A, const float* 
   return launch_hmm_code_sample(log_pi, log_A, log_B, uniforms, N, T, S, V, states, codes, (hipStream_t)stream);
 }
 
+size_t vqhmm_code_viterbi_workspace_size(int64_t B, int64_t T, int64_t S, int64_t V) {
+  return hmm_code_viterbi_ws_bytes(B, T, S, V);
+}
+
+int vqhmm_code_viterbi_f32(const float* log_pi, const float* log_A, const float* log_B, const int32_t* codes,
+                           const int64_t* lengths, int64_t B, int64_t T, int64_t S, int64_t V, int32_t* path,
+                           float* score, void* ws, size_t ws_bytes, void* stream) {
+  if (B < 0 || T < 0 || S < 0 || V < 0) return VQHMM_EINVAL;
+  if (!hmm_code_supported(S, V)) return VQHMM_EUNSUPPORTED;
+  if (B > 0 && T > 0 &&
+      (!log_pi || !log_A || !log_B || !codes || !lengths || !path || !score || !ws ||
+       ws_bytes < hmm_code_viterbi_ws_bytes(B, T, S, V)))
+    return VQHMM_EINVAL;
+  return launch_hmm_code_viterbi(log_pi, log_A, log_B, codes, lengths, B, T, S, V, path, score, ws,
+                                 (hipStream_t)stream);
+}
+
+size_t vqhmm_code_filter_workspace_size(int64_t B, int64_t T, int64_t S, int64_t V) {
+  return hmm_code_filter_ws_bytes(B, T, S, V);
+}
+
+int vqhmm_code_filter_f32(const float* log_pi, const float* log_A, const float* log_B, const int32_t* codes,
+                          const int64_t* lengths, const float* prev, int64_t B, int64_t T, int64_t S, int64_t V,
+                          float* filt, float* last, float* loglik, void* ws, size_t ws_bytes, void* stream) {
+  if (B < 0 || T < 0 || S < 0 || V < 0) return VQHMM_EINVAL;
+  if (!hmm_code_supported(S, V)) return VQHMM_EUNSUPPORTED;
+  if (B > 0 && T > 0 &&
+      ((!prev && !log_pi) || !log_A || !log_B || !codes || !lengths || !ws ||
+       ws_bytes < hmm_code_filter_ws_bytes(B, T, S, V)))
+    return VQHMM_EINVAL;
+  return launch_hmm_code_filter(log_pi, log_A, log_B, codes, lengths, prev, B, T, S, V, filt, last, loglik, ws,
+                                (hipStream_t)stream);
+}
+
 int vqhmm_ffbs_sample_f32(const float* filt, const float* log_A, const int64_t* lengths, const float* u, int64_t B,
                           int64_t T, int64_t K, int64_t N, int32_t* paths, void* stream) {
   if (B < 0 || T < 0 || K < 0 || N < 0) return VQHMM_EINVAL;

@@ -517,6 +517,16 @@ int launch_hmm_code_estep(const float* log_pi, const float* log_A, const float* 
 int launch_hmm_code_sample(const float* log_pi, const float* log_A, const float* log_B, const float* uniforms,
                            int64_t N, int64_t T, int64_t S, int64_t V, int32_t* states, int32_t* codes,
                            hipStream_t s);
+// ... its MAP path and its causal filter (hmm_code_decode.hip): path (B,T) / score (B); filt (B,T,S), last (B,S)
+// and loglik (B) nullable, prev (B,S) nullable (then log_pi is not read); ws = the matching *_ws_bytes
+size_t hmm_code_viterbi_ws_bytes(int64_t B, int64_t T, int64_t S, int64_t V);
+size_t hmm_code_filter_ws_bytes(int64_t B, int64_t T, int64_t S, int64_t V);
+int launch_hmm_code_viterbi(const float* log_pi, const float* log_A, const float* log_B, const int32_t* codes,
+                            const int64_t* lengths, int64_t B, int64_t T, int64_t S, int64_t V, int32_t* path,
+                            float* score, void* ws, hipStream_t s);
+int launch_hmm_code_filter(const float* log_pi, const float* log_A, const float* log_B, const int32_t* codes,
+                           const int64_t* lengths, const float* prev, int64_t B, int64_t T, int64_t S, int64_t V,
+                           float* filt, float* last, float* loglik, void* ws, hipStream_t s);
 int launch_clip_grad_norm(float* g, int64_t n, float pre_scale, float max_norm, float* total_out, hipStream_t s);
 int launch_adam(float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2,
                 double eps, int64_t* step, float gmul, hipStream_t s);

@@ -1,7 +1,8 @@
-"""Stationary HMM on VQ code indices: Baum-Welch EM and ancestral sampling
-(pseudocode.txt:25-32: `hmm.train_em(all_code_indices)`, `hmm.sample(seq_len)`; math.md:23-62 with
-M_t = M).  HIP only: the E-step and the sampler are the fused kernels of hmm_code.hip
-(vqhmm_code_estep_f32 / vqhmm_code_sample_f32, contracts in include/vqhmm.h); the M-step is
+"""Stationary HMM on VQ code indices: Baum-Welch EM, ancestral sampling, Viterbi decode and the
+streaming causal filter (pseudocode.txt:25-32: `hmm.train_em(all_code_indices)`, `hmm.sample(seq_len)`;
+math.md:23-62 with M_t = M).  HIP only: the E-step and the sampler are the fused kernels of hmm_code.hip
+(vqhmm_code_estep_f32 / vqhmm_code_sample_f32), decode and filter those of hmm_code_decode.hip
+(vqhmm_code_viterbi_f32 / vqhmm_code_filter_f32), contracts in include/vqhmm.h; the M-step is
 S*S + S*V numbers of torch arithmetic in fp64 on the device.
 """
 import torch
@@ -91,6 +92,73 @@ class CodeHMM(torch.nn.Module):
         """gamma (B,T,S) fp32: p(z_t = s | codes[b, :lengths[b]]), rows at t >= length are 0."""
         codes, lengths, B, T = self._inputs(codes, lengths)
         return self._estep(codes, lengths, B, T, False, True)["gamma"]
+
+    # ------------------------------------------------------- decode and filter
+    def decode(self, codes, lengths=None):
+        """MAP state path (Viterbi, vqhmm_code_viterbi_f32) -> (path (B,T) int32 with -1 at t >= length,
+        score (B,) fp32 = the path's log weight).  Length 0: score -inf; a code outside [0, V) inside the
+        length: path all -1 and score NaN."""
+        codes, lengths, B, T = self._inputs(codes, lengths)
+        S, V = self.num_states, self.num_codes
+        dev = codes.device
+        path = torch.empty((B, T), dtype=torch.int32, device=dev)
+        score = torch.empty((B,), dtype=torch.float32, device=dev)
+        lib = _ext.load()
+        nb = lib.vqhmm_code_viterbi_workspace_size(B, T, S, V)
+        ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=dev)
+        with torch.no_grad():
+            _ext.check(lib.vqhmm_code_viterbi_f32(
+                _ext.ptr(self.log_pi), _ext.ptr(self.log_A), _ext.ptr(self.log_B), _ext.ptr(codes), _ext.ptr(lengths),
+                B, T, S, V, _ext.ptr(path), _ext.ptr(score), _ext.ptr(ws), nb, _ext.stream_ptr(dev)),
+                "CodeHMM.decode")
+        return path, score
+
+    def _filter(self, codes, lengths, state, want_filt):
+        codes, lengths, B, T = self._inputs(codes, lengths)
+        S, V = self.num_states, self.num_codes
+        dev = codes.device
+        if state is not None:
+            if not torch.is_tensor(state) or state.shape != (B, S) or state.dtype != torch.float32:
+                raise ValueError(f"CodeHMM: state must be a ({B}, {S}) float32 tensor")
+            _ext.require_device(state)
+            state = state.contiguous()
+        filt = torch.empty((B, T, S), dtype=torch.float32, device=dev) if want_filt else None
+        last = torch.empty((B, S), dtype=torch.float32, device=dev)
+        loglik = torch.empty((B,), dtype=torch.float32, device=dev)
+        lib = _ext.load()
+        nb = lib.vqhmm_code_filter_workspace_size(B, T, S, V)
+        ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=dev)
+        with torch.no_grad():
+            _ext.check(lib.vqhmm_code_filter_f32(
+                _ext.ptr(self.log_pi), _ext.ptr(self.log_A), _ext.ptr(self.log_B), _ext.ptr(codes), _ext.ptr(lengths),
+                _ext.ptr(state), B, T, S, V, _ext.ptr(filt), _ext.ptr(last), _ext.ptr(loglik), _ext.ptr(ws), nb,
+                _ext.stream_ptr(dev)), "CodeHMM.filter")
+        return filt, last, loglik
+
+    def filter(self, codes, lengths=None, state=None, return_state=False):
+        """Causal filter (vqhmm_code_filter_f32): filt (B,T,S) fp32 with filt[b,t] = p(z_t | codes[b, :t+1]) (no
+        look-ahead; rows at t >= length are 0) and loglik (B,) = log p(codes[b, :length] | state).  `state`
+        (B,S) fp32 is the carry of the previous chunk (None: the sequence starts from log_pi); with
+        return_state the new carry filt[b, length-1] is returned too, and feeding it back gives what one call
+        on the concatenated codes gives.  loglik is NaN for length 0 (the carry then passes through)."""
+        filt, last, loglik = self._filter(codes, lengths, state, True)
+        return (filt, loglik, last) if return_state else (filt, loglik)
+
+    def update(self, codes, lengths=None, state=None):
+        """The streaming form of `filter`: -> (state (B,S), loglik (B,)) without writing filt."""
+        _, last, loglik = self._filter(codes, lengths, state, False)
+        return last, loglik
+
+    @torch.no_grad()
+    def predict_next(self, state):
+        """The next code's predictive distribution (B,V) fp32 from a filtered state (B,S): normalise(state A) B."""
+        S = self.num_states
+        if not torch.is_tensor(state) or state.dim() != 2 or state.shape[1] != S or state.dtype != torch.float32:
+            raise ValueError(f"CodeHMM: state must be a (B, {S}) float32 tensor")
+        _ext.require_device(self.log_pi, state)
+        nxt = state @ torch.exp(self.log_A)
+        nxt = nxt / nxt.sum(-1, keepdim=True)
+        return nxt @ torch.exp(self.log_B)
 
     # ----------------------------------------------------------------- M-step
     @staticmethod
