@@ -88,7 +88,9 @@ struct SWArgs {
 };
 
 // c2_mfma_tile<1, 1, 4, 3, ST_LDW, 16>'s pipelined sequence on a compact image holding only output rows
-// n < 4 of each tap (the full image's rows n >= 4 are zero: lanes l16 >= 4 use 0, the same bits)
+// n < 4 of each tap (the full image's rows n >= 4 are zero: lanes l16 >= 4 use 0, the same bits).  Those lanes
+// read row 0's words and the 0 is selected in the step that uses them: selected at the load, every step waited
+// for the read it had just issued.
 __device__ __forceinline__ void c2_tile_n4(const float* Wc, const float* Xw, int lg4, int l16, f32x4& acc) {
   constexpr int KCP = 4, NSTEP = 3 * KCP;
   const bool live = l16 < 4;
@@ -97,8 +99,7 @@ __device__ __forceinline__ void c2_tile_n4(const float* Wc, const float* Xw, int
   auto load = [&](int st, float4& a, float4& b) __attribute__((always_inline)) {
     const int tap = st / KCP, kk = st - tap * KCP;
     const int col = kk * 16 + 4 * lg4;
-    const float4 w = *reinterpret_cast<const float4*>(Wc + (tap * 4 + wrow) * ST_LDW + col);
-    a = live ? w : make_float4(0.f, 0.f, 0.f, 0.f);
+    a = *reinterpret_cast<const float4*>(Wc + (tap * 4 + wrow) * ST_LDW + col);
     b = *reinterpret_cast<const float4*>(Xw + (l16 + tap) * ST_LDW + col);
   };
   load(0, av[0], bv[0]);
@@ -107,68 +108,146 @@ __device__ __forceinline__ void c2_tile_n4(const float* Wc, const float* Xw, int
     const int cb = st & 1;
     if (st + 1 < NSTEP) load(st + 1, av[cb ^ 1], bv[cb ^ 1]);
     __builtin_amdgcn_sched_barrier(0);
-    acc = mfma16x16x4(av[cb].x, bv[cb].x, acc);
-    acc = mfma16x16x4(av[cb].y, bv[cb].y, acc);
-    acc = mfma16x16x4(av[cb].z, bv[cb].z, acc);
-    acc = mfma16x16x4(av[cb].w, bv[cb].w, acc);
+    const float4 au = live ? av[cb] : make_float4(0.f, 0.f, 0.f, 0.f);
+    acc = mfma16x16x4(au.x, bv[cb].x, acc);
+    acc = mfma16x16x4(au.y, bv[cb].y, acc);
+    acc = mfma16x16x4(au.z, bv[cb].z, acc);
+    acc = mfma16x16x4(au.w, bv[cb].w, acc);
     __builtin_amdgcn_sched_barrier(0);
   }
 }
 
-// One wave's tiles of a weight gradient over the owned window rows [lo, lo + 4 nstep): per 4-row step one
-// MFMA per tile, lane group lg4 taking row lo + 4 k + rm; A = fa(row) (dY[row][o] of this lane's output
-// channel), B of tile t = fb(row, t) (X[row + tap - 1][c]); bacc += A (the bias gradient's partial).  The
-// next step's operands are read while this step's MFMAs run (two register sets, unrolled by two; the
-// read past the last step is clamped to it).
-template <int NT, class FA, class FB>
-__device__ __forceinline__ void wg_pass(int lo, int nstep, int rm, FA fa, FB fb, f32x4 (&acc)[NT], float& bacc) {
-  float a0, a1, b0[NT], b1[NT];
-  auto load = [&](int k, float& av, float (&bv)[NT]) __attribute__((always_inline)) {
-    const int row = lo + 4 * k + rm;
-    av = fa(row);
+// An LDS address: 32-bit arithmetic, and a constant index becomes the read's immediate offset
+typedef const __attribute__((address_space(3))) float* ldsp;
+__device__ __forceinline__ ldsp to_lds(const float* p) { return (ldsp)p; }
+enum { SEL_NONE = 0, SEL_A = 1, SEL_B = 2 };  // which operand of a pass has structurally-zero lanes
+
+// One wave's tiles of a weight gradient over the owned window rows: nstep 4-row steps, one MFMA per tile per
+// step, lane group lg4 taking row lo + 4 k + rm of step k; A = dY[row][o] of this lane's output channel, B of
+// tile t = X[row + tap - 1][c]; bacc += A (the bias gradient's partial).
+// The operands are read through two running LDS addresses: pa / pb are this lane's operands of step 0 and move
+// by ga / gb floats per group of four steps; fa(pa, j) / fb(pb, j, t) read step j (0..3, a constant once
+// unrolled) of the group, so every read is base + immediate and a step has no address arithmetic.  A
+// structurally-zero lane (SEL names its operand, ok is false on it) reads a real word and uses 0: the select
+// is applied in the step that USES the word, behind that step's counted wait; at the load it would make
+// every step wait for the read it has just issued.
+// Steps are read in order and used in order (the same k order, so the same sums), and no row past the last
+// step's is read: the loops run while a whole group of reads lies ahead, the last steps are peeled.
+template <int NT, int SEL, class FA, class FB>
+__device__ __forceinline__ void wg_pass(int nstep, ldsp pa, ldsp pb, int ga, int gb, FA fa, FB fb, bool ok,
+                                        f32x4 (&acc)[NT], float& bacc) {
+  constexpr int NS = NT == 1 ? 4 : 2;  // operand sets: step k lives in set k % NS
+  float ar[NS], br[NS][NT];
+  // the running addresses are opaque to the compiler where they change: it otherwise splits them into a loop
+  // counter plus a constant too large for a read's immediate, and adds the two up again in front of every read
+  auto hide = [](ldsp& p) __attribute__((always_inline)) { asm volatile("" : "+v"(p)); };
+  auto load_at = [&](int j, ldsp qa, ldsp qb) __attribute__((always_inline)) {  // step j of the group at qa / qb
+    ar[j % NS] = fa(qa, j);
 #pragma unroll
-    for (int t = 0; t < NT; ++t) bv[t] = fb(row, t);
+    for (int t = 0; t < NT; ++t) br[j % NS][t] = fb(qb, j, t);
   };
-  auto mma = [&](float av, const float (&bv)[NT]) __attribute__((always_inline)) {
+  auto load = [&](int j) __attribute__((always_inline)) { load_at(j, pa, pb); };
+  auto next = [&]() __attribute__((always_inline)) {
+    pa += ga;
+    pb += gb;
+    hide(pa);
+    hide(pb);
+  };
+  hide(pa);
+  hide(pb);
+  auto mma = [&](int j) __attribute__((always_inline)) {
+    const float av = (SEL == SEL_A && !ok) ? 0.f : ar[j % NS];
     bacc += av;
 #pragma unroll
-    for (int t = 0; t < NT; ++t) acc[t] = mfma16x16x4(av, bv[t], acc[t]);
+    for (int t = 0; t < NT; ++t) acc[t] = mfma16x16x4(av, (SEL == SEL_B && !ok) ? 0.f : br[j % NS][t], acc[t]);
   };
   if constexpr (NT == 1) {
-    // one 32-cycle MFMA per step cannot hide an LDS read one step ahead: a ring of four operand sets
-    // (three steps' reads in flight), the same k order (so the same sums)
-    float ar[4], br[4][1];
+    // one 32-cycle MFMA per step cannot hide an LDS read one step ahead: a ring of four operand sets, three
+    // steps' reads in flight behind the one being used
+    if (nstep < 4) {  // shorter than the ring
 #pragma unroll
-    for (int j = 0; j < 4; ++j) load(min(j, nstep - 1), ar[j], br[j]);
-    int k = 0;
-    for (; k + 4 <= nstep; k += 4) {
+      for (int j = 0; j < 3; ++j)
+        if (j < nstep) load(j);
+#pragma unroll
+      for (int j = 0; j < 3; ++j)
+        if (j < nstep) mma(j);
+      return;
+    }
+    // (the reads of two steps kept apart: merged into one two-word read here and not in the loop, they would
+    // make the loop's first wait count for this order of issue and not for its own)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      load(j);
+      asm volatile("" ::: "memory");
+    }
+    next();
+    int k = 0;  // set j holds step k + j
+    for (; k + 8 <= nstep; k += 4) {
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         __builtin_amdgcn_sched_barrier(0);
-        mma(ar[j], br[j]);
+        mma(j);
         __builtin_amdgcn_sched_barrier(0);
-        load(min(k + 4 + j, nstep - 1), ar[j], br[j]);  // reads past the last step are clamped to it (unused)
+        load(j);  // step k + 4 + j
       }
+      next();
+    }
+    // 4..7 steps left, the first four of them read.  The last rem = 0..3 reads are issued without a branch,
+    // so that these steps' waits stay counted too: a set past them reads its step of the group before again
+    // (a word that exists; not used)
+    const int rem = nstep - k - 4;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      __builtin_amdgcn_sched_barrier(0);
+      mma(j);
+      __builtin_amdgcn_sched_barrier(0);
+      if (j < 3) load_at(j, j < rem ? pa : pa - ga, j < rem ? pb : pb - gb);
     }
 #pragma unroll
-    for (int j = 0; j < 3; ++j)
-      if (k + j < nstep) mma(ar[j], br[j]);
-    (void)a0; (void)a1; (void)b0; (void)b1;
+    for (int j = 0; j < 3; ++j) {
+      __builtin_amdgcn_sched_barrier(0);
+      if (j < rem) mma(j);
+    }
     return;
   }
-  load(0, a0, b0);
-  int k = 0;
-  for (; k + 1 < nstep; k += 2) {
-    load(k + 1, a1, b1);
+  // two sets: the next step's operands are read while this step's NT MFMAs run
+  load(0);
+  int k = 0;  // set 0 holds step k, the group's step 0
+  for (; k + 5 <= nstep; k += 4) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (j == 3) next();
+      load((j + 1) & 3);  // step k + j + 1
+      __builtin_amdgcn_sched_barrier(0);
+      mma(j);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+  const int rem = nstep - k;  // 1..4 steps left, the first of them read
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    if (j < 3 && j + 1 < rem) load(j + 1);
     __builtin_amdgcn_sched_barrier(0);
-    mma(a0, b0);
-    __builtin_amdgcn_sched_barrier(0);
-    load(min(k + 2, nstep - 1), a0, b0);
-    __builtin_amdgcn_sched_barrier(0);
-    mma(a1, b1);
+    if (j < rem) mma(j);
     __builtin_amdgcn_sched_barrier(0);
   }
-  if (k < nstep) mma(a0, b0);
+}
+
+// dma16 kept out of the compiler's count of memory operations.  While a global_load_lds it knows of is
+// outstanding in vmcnt, the compiler takes lgkmcnt for out of order as well (the instruction is FLAT-encoded
+// and has an LDS operand) and turns every wait for an LDS read into lgkmcnt(0): dec_conv2's pass in P2, which
+// runs under the image's DMA, then waited for the reads it had just issued on every other step.  The caller
+// waits for these with its own vmcnt; loads the compiler counts wait at most longer for being counted short.
+// One 1-KB chunk per wave: lane l copies the 16 bytes at src + off (off = 16 l) to dst + 16 l; src and dst are
+// wave-uniform.  (s_nop 4: an SGPR written by a VALU instruction just ahead is not read early as an address.)
+__device__ __forceinline__ void dma16_uncounted(const float* src, int off, float* dst) {
+  const unsigned d = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) float*)dst);
+  unsigned keep;
+  asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
+               "global_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep)
+               : "v"(off), "s"(d), "s"(src)
+               : "memory");
 }
 
 // the lane-group partials of a bias column summed in a fixed order: (g0 + g1) + (g2 + g3) on every lane
@@ -265,9 +344,9 @@ __global__ __launch_bounds__(512) void strip_bwdw_kernel(SWArgs a, ConvArgs f) {
     constexpr int N1 = 3 * 64 * ST_LDW / 4, C1 = N1 / 64;
     static_assert(N1 % 64 == 0 && C1 <= 56, "7 whole chunks per wave");
 #pragma unroll
-    for (int j = 0; j < 7; ++j) {  // unguarded (no branch join: the compiler counts these exactly)
-      const int c = min(wave + 8 * j, C1 - 1);
-      dma16(a.img_d2 + 4 * (c * 64 + lane), sh.RW + c * 256);
+    for (int j = 0; j < 7; ++j) {  // unguarded: 7 vmcnt events in every wave, counted by hand below
+      const int c = min(__builtin_amdgcn_readfirstlane(wave) + 8 * j, C1 - 1);
+      dma16_uncounted(a.img_d2 + c * 256, 16 * lane, sh.RW + c * 256);
     }
   };
 
@@ -371,6 +450,7 @@ __global__ __launch_bounds__(512) void strip_bwdw_kernel(SWArgs a, ConvArgs f) {
     const float lsc = (f.lb_scale ? f.lb_scale : &g_bwdw_one)[z0];
     const int lane = tidv & 63, lg4 = lane >> 4, l16 = lane & 15;
     const int rm = ((lg4 & 1) << 1) | (lg4 >> 1);  // rows 2 apart in each 32-lane half: conflict-free b32 reads
+    const int row0 = lo + rm;  // this lane's window row in a weight-gradient pass's step 0 (step k: row0 + 4 k)
     const int qtap = l16 / K, qc = l16 - qtap * K;
     const bool qok = l16 < 3 * K;
     const int xtap = l16 / D, xc = l16 - xtap * D;
@@ -454,9 +534,13 @@ __global__ __launch_bounds__(512) void strip_bwdw_kernel(SWArgs a, ConvArgs f) {
     {  // tiles (ob = wave / 2, cb = 2 (wave % 2) + j, tap): dY = dg2 (slots), X = g1 (G1)
       const float* ya = sh.RS + (wave >> 1) * 16 + l16;
       const float* xb = sh.RG + (wave & 1) * 32 + l16;
-      wg_pass<6>(lo, nstep, rm,
-                 [&](int row) { return ya[(row >> 4) * 18 * ST_LDW + ((row & 15) + 1) * ST_LDW]; },
-                 [&](int row, int t) { return xb[(row - 1 + t % 3) * ST_LDW + (t / 3) * 16]; }, accD2, bD2);
+      // dg2 row `row` is slot row (row & 15) + 1 of slot block row >> 4 (18 rows each): a lane's four rows of a
+      // group, row0 + 4 j, stay in one block for j < 3, and the fourth is in the next one unless rm = 0 (row 15)
+      const int a3 = (rm == 0 ? 12 : 14) * ST_LDW;
+      wg_pass<6, SEL_NONE>(nstep, to_lds(ya + (row0 + 1) * ST_LDW), to_lds(xb + (row0 - 1) * ST_LDW), 18 * ST_LDW,
+                           16 * ST_LDW, [&](ldsp p, int j) { return j < 3 ? p[4 * j * ST_LDW] : p[a3]; },
+                           [&](ldsp p, int j, int t) { return p[(4 * j + t % 3) * ST_LDW + (t / 3) * 16]; }, true,
+                           accD2, bD2);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every wave's share of the image has landed
     lds_barrier_dma();
@@ -521,14 +605,16 @@ __global__ __launch_bounds__(512) void strip_bwdw_kernel(SWArgs a, ConvArgs f) {
     if (wave < 4) {  // to_params: tile (0, cb = wave), 1x1: dY = dpar (DP), X = g2 (G2)
       const float* ya = sh.RW + RW_DP + l16;
       const float* xb = sh.RW + wave * 16 + l16;
-      wg_pass<1>(lo, nstep, rm, [&](int row) { return ya[row * SW_LDD]; },
-                 [&](int row, int) { return xb[row * ST_LDW]; }, accS0, bS0);
+      wg_pass<1, SEL_NONE>(nstep, to_lds(ya + row0 * SW_LDD), to_lds(xb + row0 * ST_LDW), 16 * SW_LDD, 16 * ST_LDW,
+                           [&](ldsp p, int j) { return p[4 * j * SW_LDD]; },
+                           [&](ldsp p, int j, int) { return p[4 * j * ST_LDW]; }, true, accS0, bS0);
     } else {  // composed dec_conv1: tile (ob = wave - 4, packed taps): dY = dg1 (D1), X = q (Q)
       const float* ya = sh.RS + ST_LDW + (wave - 4) * 16 + l16;
       const float* xb = sh.RE + qc;
-      wg_pass<1>(lo, nstep, rm, [&](int row) { return ya[row * ST_LDW]; },
-                 [&](int row, int) { const float v = xb[(row - 1 + (qok ? qtap : 0)) * SW_LDQ]; return qok ? v : 0.f; },
-                 accS0, bS0);
+      // (lanes past the 3 K packed columns read tap 0's word and use 0)
+      wg_pass<1, SEL_B>(nstep, to_lds(ya + row0 * ST_LDW), to_lds(xb + (row0 - 1 + (qok ? qtap : 0)) * SW_LDQ),
+                        16 * ST_LDW, 16 * SW_LDQ, [&](ldsp p, int j) { return p[4 * j * ST_LDW]; },
+                        [&](ldsp p, int j, int) { return p[4 * j * SW_LDQ]; }, qok, accS0, bS0);
     }
     float4 m2[4];  // h1e rows: H1 in P5, enc_conv2 dgrad's mask in P6
     load_mask(a.h1e, rb, R, lg4, l16, m2);
@@ -569,15 +655,16 @@ __global__ __launch_bounds__(512) void strip_bwdw_kernel(SWArgs a, ConvArgs f) {
     {  // tiles (ob = wave % 2, cb = wave / 2, tap): dY = dh2 (Dh2), X = h1e (H1)
       const float* ya = sh.RD + SB_LDE + (wave & 1) * 16 + l16;
       const float* xb = sh.RW + (wave >> 1) * 16 + l16;
-      wg_pass<3>(lo, nstep, rm, [&](int row) { return ya[row * SB_LDE]; },
-                 [&](int row, int t) { return xb[(row - 1 + t) * ST_LDW]; }, accE2, bE2);
+      wg_pass<3, SEL_NONE>(nstep, to_lds(ya + row0 * SB_LDE), to_lds(xb + (row0 - 1) * ST_LDW), 16 * SB_LDE, 16 * ST_LDW,
+                           [&](ldsp p, int j) { return p[4 * j * SB_LDE]; },
+                           [&](ldsp p, int j, int t) { return p[(4 * j + t) * ST_LDW]; }, true, accE2, bE2);
     }
     if (wave < 2) {  // to_logits: tile (0, cb = wave), 1x1: dY = dlog (DL, channels < K), X = h2e (H2)
       const float* ya = sh.RW + RW_DL + min(l16, 3);
       const float* xb = sh.RS + wave * 16 + l16;
-      const bool ok = l16 < K;
-      wg_pass<1>(lo, nstep, rm, [&](int row) { const float v = ya[row * SW_LDQ]; return ok ? v : 0.f; },
-                 [&](int row, int) { return xb[row * SB_LDE]; }, accS1, bS1);
+      wg_pass<1, SEL_A>(nstep, to_lds(ya + row0 * SW_LDQ), to_lds(xb + row0 * SB_LDE), 16 * SW_LDQ, 16 * SB_LDE,
+                        [&](ldsp p, int j) { return p[4 * j * SW_LDQ]; },
+                        [&](ldsp p, int j, int) { return p[4 * j * SB_LDE]; }, l16 < K, accS1, bS1);
     }
     lds_barrier();  // B6: H1, H2, DL, Dh2 and the enc_conv2 image are read
     if (it == a.prof_it) stamp<PROF>(6);
@@ -589,7 +676,10 @@ __global__ __launch_bounds__(512) void strip_bwdw_kernel(SWArgs a, ConvArgs f) {
     if (last) {  // after the loop: decoder.conv1's weight (64, 64, 3) for the dE share (LDS DMA, 48 chunks of 1 KB),
       // the share's dWc buffer zeroed (RG: the enc_conv2 image is read)
 #pragma unroll
-      for (int j = 0; j < 6; ++j) dma16(a.cmpW + 4 * ((wave + 8 * j) * 64 + lane), sh.RW + (wave + 8 * j) * 256);
+      for (int j = 0; j < 6; ++j) {  // (uncounted, as the image's: P8's pass runs under it; waited for after the loop)
+        const int c = __builtin_amdgcn_readfirstlane(wave) + 8 * j;
+        dma16_uncounted(a.cmpW + c * 256, 16 * lane, sh.RW + c * 256);
+      }
       for (int i = tidv; i < 1536; i += 512) sh.RG[i] = 0.f;
     }
     lds_barrier_dma();  // B7 (the next strip's image DMA stays in flight: waited before B1)
@@ -598,9 +688,9 @@ __global__ __launch_bounds__(512) void strip_bwdw_kernel(SWArgs a, ConvArgs f) {
     if (wave >= 4) {
       const float* ya = sh.RS + (wave - 4) * 16 + l16;
       const float* xb = sh.RD + xc;
-      wg_pass<1>(lo, nstep, rm, [&](int row) { return ya[row * ST_LDW]; },
-                 [&](int row, int) { const float v = xb[(row - 1 + (xok ? xtap : 0)) * SW_LDQ]; return xok ? v : 0.f; },
-                 accS1, bS1);
+      wg_pass<1, SEL_B>(nstep, to_lds(ya + row0 * ST_LDW), to_lds(xb + (row0 - 1 + (xok ? xtap : 0)) * SW_LDQ),
+                        16 * ST_LDW, 16 * SW_LDQ, [&](ldsp p, int j) { return p[4 * j * ST_LDW]; },
+                        [&](ldsp p, int j, int) { return p[4 * j * SW_LDQ]; }, xok, accS1, bS1);
     }
     lds_barrier_dma();  // B8: DH1 and XX are read before the next strip writes the slots
     if (it == a.prof_it) stamp<PROF>(7);
