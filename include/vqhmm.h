@@ -291,6 +291,65 @@ int vqhmm_code_sample_f32(const float* log_pi, const float* log_A, const float* 
                           const float* uniforms, int64_t N, int64_t T, int64_t S, int64_t V,
                           int32_t* states, int32_t* codes, void* stream);
 
+/* -------------------------------------------------- codebook learning ----
+ * Per-code statistics of a batch under given assignments, the quantizer's backward from the same
+ * pass, and the channels-first lookup (pseudocode.txt:8-32, the codebook's side; vq_codebook.hip).
+ * z (B,Dv,T) channels-first fp32, idx (B,T) int32 as vqhmm_vq_argmin_f32 writes them, lengths (B)
+ * int64 (nullable: every t counts), codebook (K,Dv) fp32.  1 <= K <= 65536, 1 <= Dv <= 512,
+ * K*Dv <= 2^21 (else VQHMM_EUNSUPPORTED, and the workspace queries return 0).
+ *
+ * A position (b,t) counts when t < clamp(lengths[b], 0, T) and 0 <= idx[b,t] < K; idx at
+ * t >= length is never read.  Its residual is r_d = fl32(z[b,d,t] - codebook[idx[b,t]][d]).
+ *
+ * vqhmm_vq_stats_f32: every element of
+ *   count[k]  (K)    = the number of counted positions with idx = k
+ *   rsum[k,d] (K,Dv) = sum of r_d over those positions
+ *   *sse      (1, nullable) = sum of r_d^2 over all counted positions
+ * is written, in fp64 (the caller never clears them).  The residual form serves every update rule
+ * without the cancellation of sum z - count c: the codebook gradient of the MSE is -(2 g / n) rsum,
+ * the per-code mean is c + rsum / count, the plain sum is rsum + count c.
+ *
+ * vqhmm_vq_quantize_bwd_f32: the same pass, writing
+ *   dz[b,d,t]      = fl(g + fl(s * r_d))    g = g_zq[b,d,t] (0 with g_zq NULL), s = *dz_scale,
+ *                                           r_d = 0 at positions that do not count
+ *   dcodebook[k,d] = (float)(*dcb_scale * rsum[k,d])    (the product in fp64)
+ * dz (B,Dv,T) and dcodebook (K,Dv) are each nullable; every element of the ones given is written; dz
+ * may alias g_zq.  dz is two fp32 roundings, never contracted.  dz_scale and dcb_scale point to device
+ * floats, so a caller whose scales are device scalars (autograd's incoming gradients) needs no host
+ * sync.  With s = 2 beta g_commit / n and *dcb_scale = -2 g_cb / n this is the backward of
+ * vqhmm_vq_quantize_f32's two losses over n = B Dv T elements plus the straight-through gradient.
+ *
+ * Accumulation: every addition into a bin is fp64, made in position order by the one lane that owns
+ * the bin's channel in the one wave that owns the bin's code; tiles of 64 positions are assigned to
+ * workgroups statically, each workgroup fills one slab and a second launch adds the workgroups'
+ * slabs in a fixed order.  No float atomics: the same inputs give the same bits every run.
+ * The slab lives in LDS when (K*Dv + K + 1)*8 bytes fit beside the 16.25 KB staging tile (K*(Dv+1) <= 17887: 256 x 64, 512 x 32)
+ * and in the workgroup's partial in the workspace otherwise.  Graph-capturable, no host sync, 64-bit
+ * offsets, z / g_zq / dz touched only at t < T, the codebook only at rows in [0, K).
+ * Workspace: vqhmm_vq_stats_workspace_size / vqhmm_vq_quantize_bwd_workspace_size bytes (the
+ * partials, at most 64 MB unless one partial is larger).
+ *
+ * vqhmm_vq_lookup_f32: out[b,d,t] = codebook[idx[b,t]][d] (B,Dv,T) fp32, 0 where idx is outside
+ * [0, K) (vqhmm_code_viterbi_f32's and CodeHMM's -1 padding); every element written.  No workspace.
+ *
+ * Return codes, checked in this order on the host before any launch: a negative size ->
+ * VQHMM_EINVAL; K, Dv or K*Dv out of range -> VQHMM_EUNSUPPORTED; B*T == 0 -> VQHMM_OK with the
+ * given outputs zeroed and no kernel launch; a null required pointer (z, idx, codebook, count, rsum;
+ * dz_scale, dcb_scale; out) -> VQHMM_EINVAL; a null or short workspace -> VQHMM_EWORKSPACE. */
+size_t vqhmm_vq_stats_workspace_size(int64_t B, int64_t Dv, int64_t T, int64_t K);
+int vqhmm_vq_stats_f32(const float* z, const int32_t* idx, const int64_t* lengths,
+                       int64_t B, int64_t Dv, int64_t T, const float* codebook, int64_t K,
+                       double* count, double* rsum, double* sse,
+                       void* workspace, size_t ws_bytes, void* stream);
+size_t vqhmm_vq_quantize_bwd_workspace_size(int64_t B, int64_t Dv, int64_t T, int64_t K);
+int vqhmm_vq_quantize_bwd_f32(const float* z, const int32_t* idx, const int64_t* lengths,
+                              int64_t B, int64_t Dv, int64_t T, const float* codebook, int64_t K,
+                              const float* g_zq, const float* dz_scale, const float* dcb_scale,
+                              float* dz, float* dcodebook,
+                              void* workspace, size_t ws_bytes, void* stream);
+int vqhmm_vq_lookup_f32(const float* codebook, int64_t K, int64_t Dv, const int32_t* idx,
+                        int64_t B, int64_t T, float* out, void* stream);
+
 /* ------------------------------------------------------- training step ----
  * compute_loss forward + backward of VAE_HMM (VQ_VAE_HMM_fixed.py:106-137,
  * autograd of :156) as one native executor over hand-written kernels.

@@ -12,6 +12,11 @@
     python tools/kbench.py sample --B 512 --T 512 --K 8 --N 64
                                                         (the FFBS and simulation kernels, the filter beside them,
                                                          and a plain-torch FFBS loop on the same shapes)
+    python tools/kbench.py vq_stats --B 2048 --Dv 64 --T 200 --K 32 [--old-route]
+    python tools/kbench.py vq_bwd --B 2048 --Dv 64 --T 200 --K 32 [--old-route]
+                                                        (the codebook statistics / the quantizer's fused backward;
+                                                         --old-route: also bincount + index_add_ / the torch backward
+                                                         of vqhmm.quantize, in five alternating pairs)
 """
 import argparse
 import json
@@ -325,6 +330,104 @@ def bench_code_filter(a):
     _bench_code_decode(a, "code_filter")
 
 
+def _bench_vq_codebook(a, leg):
+    """vqhmm_vq_stats_f32 or vqhmm_vq_quantize_bwd_f32 on the argmin's indices of random z.  --old-route: also
+    the torch route to the same numbers (vq_stats: bincount + a permuted index_add_ of the residuals in fp64;
+    vq_bwd: _Quantize.backward, the gather, the permuted difference and the fp32 index_add_), in five alternating
+    pairs after a warm-up, every pair's two times reported, and a line that checks the two routes agree on the
+    timed inputs.  Algorithmic HBM bytes per position: z read (4 Dv) and the code (4); the backward also reads
+    g_zq and writes dz (8 Dv)."""
+    B, Dv, T, K = a.B, a.Dv, a.T, a.K
+    g = torch.Generator(device="cuda").manual_seed(1234)
+    z = torch.randn(B, Dv, T, device="cuda", generator=g)
+    cb = torch.randn(K, Dv, device="cuda", generator=g)
+    g_zq = torch.randn(B, Dv, T, device="cuda", generator=g)
+    idx = vqhmm.vq_argmin(z, cb)
+    il = idx.long()
+    lib = vqhmm._ext.load()
+    P = vqhmm._ext.ptr
+    st = vqhmm._ext.stream_ptr()
+    n = float(z.numel())
+    beta = 0.25
+    if leg == "vq_stats":
+        flat = torch.empty(K + K * Dv + 1, dtype=torch.float64, device="cuda")
+        nb = lib.vqhmm_vq_stats_workspace_size(B, Dv, T, K)
+        ws = torch.empty(max(nb, 8), dtype=torch.uint8, device="cuda")
+
+        def new():
+            lib.vqhmm_vq_stats_f32(P(z), P(idx), None, B, Dv, T, P(cb), K, P(flat[:K]), P(flat[K:K + K * Dv]),
+                                   P(flat[K + K * Dv:]), P(ws), nb, st)
+
+        def old():
+            count = torch.bincount(il.reshape(-1), minlength=K).double()
+            r = (z - cb[il].permute(0, 2, 1)).permute(0, 2, 1).reshape(-1, Dv).double()
+            rsum = torch.zeros(K, Dv, dtype=torch.float64, device="cuda").index_add_(0, il.reshape(-1), r)
+            return count, rsum, (r * r).sum()
+
+        out_bytes = 0
+    else:
+        dz = torch.empty_like(z)
+        dcb = torch.empty_like(cb)
+        one = torch.ones((), device="cuda")
+        dzs = torch.full((1,), 2.0 * beta / n, device="cuda")
+        dcs = torch.full((1,), -2.0 / n, device="cuda")
+        nb = lib.vqhmm_vq_quantize_bwd_workspace_size(B, Dv, T, K)
+        ws = torch.empty(max(nb, 8), dtype=torch.uint8, device="cuda")
+
+        def new():
+            lib.vqhmm_vq_quantize_bwd_f32(P(z), P(idx), None, B, Dv, T, P(cb), K, P(g_zq), P(dzs), P(dcs), P(dz),
+                                          P(dcb), P(ws), nb, st)
+
+        class Ctx:
+            saved_tensors = (z, cb, idx)
+            needs_input_grad = (True, True, False)
+
+        Ctx.beta, Ctx.n = beta, n
+        from vqhmm.hmm import _Quantize
+
+        def old():
+            return _Quantize.backward(Ctx, g_zq, None, one, one)
+
+        out_bytes = 8 * Dv
+    legs = {leg: new}
+    if a.old_route:
+        legs["old_route"] = old
+        ref = old()
+        new()
+        torch.cuda.synchronize()
+        if leg == "vq_stats":
+            chk = {"count_equal": bool(torch.equal(ref[0], flat[:K])),
+                   "rsum_maxdiff": (ref[1].reshape(-1) - flat[K:K + K * Dv]).abs().max().item(),
+                   "sse_rel": abs((ref[2] - flat[-1]).item()) / max(flat[-1].item(), 1e-300)}
+        else:
+            chk = {"dz_maxdiff": (ref[0] - dz).abs().max().item(), "dcb_maxdiff": (ref[1] - dcb).abs().max().item(),
+                   "dcb_max": dcb.abs().max().item()}
+        print(json.dumps({"check": "old_route vs " + leg, "B": B, "Dv": Dv, "T": T, "K": K, **chk}))
+    for fn in legs.values():
+        time_fn(fn, iters=3, warmup=2)
+    rounds = {k: [] for k in legs}
+    for _ in range(5):
+        for k, fn in legs.items():
+            rounds[k].append(time_fn(fn, iters=10, warmup=1))
+    t = {k: sorted(v)[len(v) // 2] for k, v in rounds.items()}
+    byts = B * T * (4 * Dv + 4 + out_bytes)
+    for k in legs:
+        rec = {"kernel": k, "B": B, "Dv": Dv, "T": T, "K": K, "us": t[k] * 1e6,
+               "pairs_us": [r * 1e6 for r in rounds[k]], "GBps": byts / t[k] / 1e9, "frac_hbm": byts / t[k] / HBM_PEAK}
+        if k == "old_route":
+            rec["x_" + leg] = t[k] / t[leg]
+            rec["fused_faster_in_every_pair"] = all(o > f for o, f in zip(rounds[k], rounds[leg]))
+        print(json.dumps(rec))
+
+
+def bench_vq_stats(a):
+    _bench_vq_codebook(a, "vq_stats")
+
+
+def bench_vq_bwd(a):
+    _bench_vq_codebook(a, "vq_bwd")
+
+
 def torch_ffbs(filt, log_A, u):
     """Plain-torch FFBS on full-length sequences, one step per iteration: a gather of the column
     z_t, a cumsum and a searchsorted (several launches per time step)."""
@@ -412,4 +515,5 @@ if __name__ == "__main__":
     a = ap.parse_args()
     {"vq": bench_vq, "stream": bench_stream, "viterbi": bench_viterbi, "fwdbwd": bench_fwdbwd,
      "filter": bench_filter, "xi": bench_xi, "estep": bench_estep, "code_viterbi": bench_code_viterbi,
-     "code_filter": bench_code_filter, "sample": bench_sample}[a.what](a)
+     "code_filter": bench_code_filter, "sample": bench_sample, "vq_stats": bench_vq_stats,
+     "vq_bwd": bench_vq_bwd}[a.what](a)

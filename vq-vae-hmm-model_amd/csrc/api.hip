@@ -444,6 +444,49 @@ int vqhmm_code_filter_f32(const float* log_pi, const float* log_A, const float* 
                                 (hipStream_t)stream);
 }
 
+size_t vqhmm_vq_stats_workspace_size(int64_t B, int64_t Dv, int64_t T, int64_t K) {
+  return vq_codebook_ws_bytes(B, Dv, T, K);
+}
+
+int vqhmm_vq_stats_f32(const float* z, const int32_t* idx, const int64_t* lengths, int64_t B, int64_t Dv, int64_t T,
+                       const float* codebook, int64_t K, double* count, double* rsum, double* sse, void* ws,
+                       size_t ws_bytes, void* stream) {
+  if (B < 0 || Dv < 0 || T < 0 || K < 0) return VQHMM_EINVAL;
+  if (!vq_codebook_supported(Dv, K)) return VQHMM_EUNSUPPORTED;
+  if (B * T > 0) {
+    if (!z || !idx || !codebook || !count || !rsum) return VQHMM_EINVAL;
+    if (!ws || ws_bytes < vq_codebook_ws_bytes(B, Dv, T, K)) return VQHMM_EWORKSPACE;
+  }
+  return launch_vq_codebook(z, idx, lengths, B, Dv, T, codebook, K, count, rsum, sse, nullptr, nullptr, nullptr,
+                            nullptr, nullptr, ws, (hipStream_t)stream);
+}
+
+size_t vqhmm_vq_quantize_bwd_workspace_size(int64_t B, int64_t Dv, int64_t T, int64_t K) {
+  return vq_codebook_ws_bytes(B, Dv, T, K);
+}
+
+int vqhmm_vq_quantize_bwd_f32(const float* z, const int32_t* idx, const int64_t* lengths, int64_t B, int64_t Dv,
+                              int64_t T, const float* codebook, int64_t K, const float* g_zq, const float* dz_scale,
+                              const float* dcb_scale, float* dz, float* dcodebook, void* ws, size_t ws_bytes,
+                              void* stream) {
+  if (B < 0 || Dv < 0 || T < 0 || K < 0) return VQHMM_EINVAL;
+  if (!vq_codebook_supported(Dv, K)) return VQHMM_EUNSUPPORTED;
+  if (B * T > 0) {
+    if (!z || !idx || !codebook || !dz_scale || !dcb_scale) return VQHMM_EINVAL;
+    if (!ws || ws_bytes < vq_codebook_ws_bytes(B, Dv, T, K)) return VQHMM_EWORKSPACE;
+  }
+  return launch_vq_codebook(z, idx, lengths, B, Dv, T, codebook, K, nullptr, nullptr, nullptr, g_zq, dz_scale,
+                            dcb_scale, dz, dcodebook, ws, (hipStream_t)stream);
+}
+
+int vqhmm_vq_lookup_f32(const float* codebook, int64_t K, int64_t Dv, const int32_t* idx, int64_t B, int64_t T,
+                        float* out, void* stream) {
+  if (B < 0 || Dv < 0 || T < 0 || K < 0) return VQHMM_EINVAL;
+  if (!vq_codebook_supported(Dv, K)) return VQHMM_EUNSUPPORTED;
+  if (B * T > 0 && (!codebook || !idx || !out)) return VQHMM_EINVAL;
+  return launch_vq_lookup(codebook, K, Dv, idx, B, T, out, (hipStream_t)stream);
+}
+
 int vqhmm_ffbs_sample_f32(const float* filt, const float* log_A, const int64_t* lengths, const float* u, int64_t B,
                           int64_t T, int64_t K, int64_t N, int32_t* paths, void* stream) {
   if (B < 0 || T < 0 || K < 0 || N < 0) return VQHMM_EINVAL;

@@ -527,6 +527,18 @@ int launch_hmm_code_viterbi(const float* log_pi, const float* log_A, const float
 int launch_hmm_code_filter(const float* log_pi, const float* log_A, const float* log_B, const int32_t* codes,
                            const int64_t* lengths, const float* prev, int64_t B, int64_t T, int64_t S, int64_t V,
                            float* filt, float* last, float* loglik, void* ws, hipStream_t s);
+// codebook learning (vq_codebook.hip), 1 <= K <= 65536, 1 <= Dv <= 512, K Dv <= 2^21: per-code count / residual
+// sum / sse in fp64 under given assignments (each nullable here), and with dz the quantizer's backward from the
+// same pass (dz = g_zq + *dz_scale r, dcb = *dcb_scale rsum from the reduce launch); ws = vq_codebook_ws_bytes.
+// launch_vq_lookup: out (B,Dv,T) = codebook[idx], 0 where idx is outside [0, K)
+bool vq_codebook_supported(int64_t Dv, int64_t K);
+size_t vq_codebook_ws_bytes(int64_t B, int64_t Dv, int64_t T, int64_t K);
+int launch_vq_codebook(const float* z, const int32_t* idx, const int64_t* lengths, int64_t B, int64_t Dv, int64_t T,
+                       const float* cb, int64_t K, double* count, double* rsum, double* sse, const float* g_zq,
+                       const float* dz_scale, const float* dcb_scale, float* dz, float* dcb, void* ws,
+                       hipStream_t s);
+int launch_vq_lookup(const float* cb, int64_t K, int64_t Dv, const int32_t* idx, int64_t B, int64_t T, float* out,
+                     hipStream_t s);
 int launch_clip_grad_norm(float* g, int64_t n, float pre_scale, float max_norm, float* total_out, hipStream_t s);
 int launch_adam(float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2,
                 double eps, int64_t* step, float gmul, hipStream_t s);

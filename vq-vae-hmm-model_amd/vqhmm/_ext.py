@@ -62,6 +62,13 @@ _SIGS = {
     "vqhmm_code_filter_workspace_size": (c_sz, [c_i64, c_i64, c_i64, c_i64]),
     "vqhmm_code_filter_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp,
                                              c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "vqhmm_vq_stats_workspace_size": (c_sz, [c_i64, c_i64, c_i64, c_i64]),
+    "vqhmm_vq_stats_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp,
+                                          c_sz, c_vp]),
+    "vqhmm_vq_quantize_bwd_workspace_size": (c_sz, [c_i64, c_i64, c_i64, c_i64]),
+    "vqhmm_vq_quantize_bwd_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp,
+                                                 c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "vqhmm_vq_lookup_f32": (ctypes.c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp]),
     "vqhmm_elbo_workspace_size": (ctypes.c_int, [ctypes.POINTER(Dims), c_i64, c_i64, ctypes.POINTER(c_sz)]),
     "vqhmm_elbo_fwd_f32": (ctypes.c_int, [ctypes.POINTER(Dims), ctypes.POINTER(c_vp), c_vp, c_vp, ctypes.c_int,
                                           c_vp, c_vp, c_i64, c_i64, c_f32, ctypes.c_int, c_vp, c_sz, c_vp, c_vp,
