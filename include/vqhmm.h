@@ -222,6 +222,23 @@ int vqhmm_markov_sample_f32(const float* log_pi, const float* log_A, const int64
  * are their sums), loglik rel 1e-5 of max(1, |loglik|).
  * Reads stay inside [0, B*T) of codes and inside the parameter arrays.
  *
+ * vqhmm_code_estep_batched_f32: the same E-step for a stack of M models (EM restarts, members of
+ * different state counts padded with -inf, the components of a mixture) on one shared (codes,
+ * lengths): log_pi (M,S), log_A (M,S,S), log_B (M,S,V) in, pi_cnt (M,S), trans_cnt (M,S,S),
+ * emit_cnt (M,S,V) fp64, loglik (M,B) and gamma (M,B,T,S) (both nullable) out, all contiguous, the
+ * member slices only 4-byte aligned.  The member is a grid dimension of the same kernel: the call
+ * is three launches whatever M is, and member m's outputs are bit-identical to vqhmm_code_estep_f32
+ * on member m's slices (which is the M = 1, weights = NULL case of it).  weights (M,B) fp32,
+ * nullable (= all 1): member m's counts are sum_b weights[m,b] * (sequence b's counts under member
+ * m), the product taken in fp64 as one fma where the contribution is added, so all-ones weights
+ * give the bits of weights = NULL.  Weights may be negative or 0 and must be finite (a non-finite
+ * weight leaves that member's counts unspecified, the other members' untouched); loglik and gamma
+ * do not depend on them.  A sequence that is impossible or has a bad code under member m
+ * contributes nothing to member m and normally to the others.  1 <= M <= 65535, else
+ * VQHMM_EUNSUPPORTED (and the workspace query returns 0).  B*T == 0: as above, per member.
+ * Workspace: vqhmm_code_estep_batched_workspace_size(B, T, S, V, M) bytes = M single-model
+ * workspaces (each rounded up to 256 bytes).  Deterministic, graph-capturable, no host sync.
+ *
  * vqhmm_code_sample_f32: ancestral sampling of N sequences of length T by inverse CDF from
  * caller-supplied uniforms (N,T,2) fp32 in [0,1): uniforms[n,t,0] draws z_t (from pi at t = 0, from
  * row z_{t-1} of A afterwards), uniforms[n,t,1] draws the code from row z_t of B.  The rule is part
@@ -287,6 +304,13 @@ int vqhmm_code_estep_f32(const float* log_pi, const float* log_A, const float* l
                          double* pi_cnt, double* trans_cnt, double* emit_cnt,
                          float* loglik, float* gamma,
                          void* workspace, size_t ws_bytes, void* stream);
+size_t vqhmm_code_estep_batched_workspace_size(int64_t B, int64_t T, int64_t S, int64_t V, int64_t M);
+int vqhmm_code_estep_batched_f32(const float* log_pi, const float* log_A, const float* log_B,
+                                 const int32_t* codes, const int64_t* lengths, const float* weights,
+                                 int64_t B, int64_t T, int64_t S, int64_t V, int64_t M,
+                                 double* pi_cnt, double* trans_cnt, double* emit_cnt,
+                                 float* loglik, float* gamma,
+                                 void* workspace, size_t ws_bytes, void* stream);
 int vqhmm_code_sample_f32(const float* log_pi, const float* log_A, const float* log_B,
                           const float* uniforms, int64_t N, int64_t T, int64_t S, int64_t V,
                           int32_t* states, int32_t* codes, void* stream);

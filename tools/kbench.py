@@ -5,6 +5,14 @@
     python tools/kbench.py estep --B 1024 --T 512 --K 8 --V 512 [--old-route]
                                                         (the fused E-step on code indices; --old-route: also
                                                          the same statistics through pairwise_posteriors)
+    python tools/kbench.py estep_batched --B 256 --T 200 --K 8 --V 512 --M 8 [--old-route]
+                                                        (M models in one vqhmm_code_estep_batched_f32 call; --old-route:
+                                                         also M sequential vqhmm_code_estep_f32 calls on the members, in
+                                                         five alternating pairs, and a line that checks the two agree
+                                                         exactly)
+    python tools/kbench.py code_fit --B 256 --T 200 --K 8 --V 512 --M 8 [--iters 20]
+                                                        (--iters EM iterations of CodeHMMEnsemble.fit against --M
+                                                         sequential CodeHMM.fit(n_init=1) runs, five alternating pairs)
     python tools/kbench.py code_viterbi --B 512 --T 512 --K 8 --V 512 [--old-route]
     python tools/kbench.py code_filter --B 2048 --T 200 --K 32 --V 512 [--old-route]
                                                         (CodeHMM's fused decode / causal filter; --old-route: also
@@ -243,6 +251,99 @@ def bench_estep(a):
                "max_us": max(rounds[k]) * 1e6, "GBps": byts[k] / t[k] / 1e9, "frac_hbm": byts[k] / t[k] / HBM_PEAK}
         if k == "old_route":
             rec["x_code_estep"] = t[k] / t["code_estep"]
+        print(json.dumps(rec))
+
+
+def _pairs(legs, rounds_n=5, iters=10):
+    """Warm every leg up, then time them alternately rounds_n times -> {leg: [seconds per call]}."""
+    for fn in legs.values():
+        time_fn(fn, iters=3, warmup=2)
+    rounds = {k: [] for k in legs}
+    for _ in range(rounds_n):
+        for k, fn in legs.items():
+            rounds[k].append(time_fn(fn, iters=iters, warmup=1))
+    return rounds
+
+
+def bench_estep_batched(a):
+    """vqhmm_code_estep_batched_f32 (counts + loglik, no gamma) on --M members of S = --K states, V = --V codes
+    that share one batch of full-length sequences.  --old-route: also --M sequential vqhmm_code_estep_f32 calls
+    on the members' slices, in five alternating pairs after a warm-up, every pair's two times reported, and a
+    check line with the largest difference between the two routes' outputs, which must be 0."""
+    B, T, S, V, M = a.B, a.T, a.K, a.V, a.M
+    g = torch.Generator(device="cuda").manual_seed(11)
+    ens = vqhmm.CodeHMMEnsemble(num_models=M, num_states=S, num_codes=V, generator=torch.Generator().manual_seed(3)).cuda()
+    codes = torch.randint(0, V, (B, T), device="cuda", generator=g, dtype=torch.int32)
+    L = torch.full((B,), T, dtype=torch.int64, device="cuda")
+    lib = vqhmm._ext.load()
+    P = vqhmm._ext.ptr
+    st = vqhmm._ext.stream_ptr()
+    cnt = [torch.empty((M, n), dtype=torch.float64, device="cuda") for n in (S, S * S, S * V)]
+    ll = torch.empty(M, B, device="cuda")
+    cnt1 = [torch.empty((M, n), dtype=torch.float64, device="cuda") for n in (S, S * S, S * V)]
+    ll1 = torch.empty(M, B, device="cuda")
+    nb = lib.vqhmm_code_estep_batched_workspace_size(B, T, S, V, M)
+    ws = torch.empty(max(nb, 1), dtype=torch.uint8, device="cuda")
+    nb1 = lib.vqhmm_code_estep_workspace_size(B, T, S, V)
+
+    def new():
+        lib.vqhmm_code_estep_batched_f32(P(ens.log_pi), P(ens.log_A), P(ens.log_B), P(codes), P(L), None, B, T, S, V, M,
+                                         P(cnt[0]), P(cnt[1]), P(cnt[2]), P(ll), None, P(ws), nb, st)
+
+    def old():
+        for m in range(M):
+            lib.vqhmm_code_estep_f32(P(ens.log_pi[m]), P(ens.log_A[m]), P(ens.log_B[m]), P(codes), P(L), B, T, S, V,
+                                     P(cnt1[0][m]), P(cnt1[1][m]), P(cnt1[2][m]), P(ll1[m]), None, P(ws), nb1, st)
+
+    legs = {"estep_batched": new}
+    if a.old_route:
+        legs["sequential"] = old
+        new()
+        old()
+        torch.cuda.synchronize()
+        diffs = [(x - y).abs().max().item() for x, y in zip(cnt + [ll], cnt1 + [ll1])]
+        print(json.dumps({"check": "sequential vs estep_batched", "B": B, "T": T, "S": S, "V": V, "M": M,
+                          "maxdiff": max(diffs)}))
+    rounds = _pairs(legs)
+    t = {k: sorted(v)[len(v) // 2] for k, v in rounds.items()}
+    for k in legs:
+        rec = {"kernel": k, "B": B, "T": T, "S": S, "V": V, "M": M, "us": t[k] * 1e6,
+               "pairs_us": [r * 1e6 for r in rounds[k]], "us_per_member": t[k] * 1e6 / M}
+        if k == "sequential":
+            rec["x_estep_batched"] = t[k] / t["estep_batched"]
+            rec["batched_faster_in_every_pair"] = all(o > f for o, f in zip(rounds[k], rounds["estep_batched"]))
+        print(json.dumps(rec))
+
+
+def bench_code_fit(a):
+    """--iters EM iterations of CodeHMMEnsemble.fit on --M members against --M sequential CodeHMM.fit(n_init=1)
+    runs from the same starts (every timed call starts from a copy of them), five alternating pairs."""
+    B, T, S, V, M, n_iter = a.B, a.T, a.K, a.V, a.M, a.iters
+    g = torch.Generator(device="cuda").manual_seed(11)
+    ens = vqhmm.CodeHMMEnsemble(num_models=M, num_states=S, num_codes=V, generator=torch.Generator().manual_seed(3)).cuda()
+    hmms = [ens.member(m) for m in range(M)]
+    start = {k: v.clone() for k, v in ens.state_dict().items()}
+    codes = torch.randint(0, V, (B, T), device="cuda", generator=g, dtype=torch.int32)
+    L = torch.full((B,), T, dtype=torch.int64, device="cuda")
+
+    def new():
+        ens.load_state_dict(start)
+        return ens.fit(codes, L, n_iter=n_iter, prior_count=1e-3)
+
+    def old():
+        for m, h in enumerate(hmms):
+            for k in ("log_pi", "log_A", "log_B"):
+                getattr(h, k).copy_(start[k][m])
+            h.fit(codes, L, n_iter=n_iter, prior_count=1e-3)
+
+    rounds = _pairs({"ensemble_fit": new, "sequential_fit": old}, iters=2)
+    t = {k: sorted(v)[len(v) // 2] for k, v in rounds.items()}
+    for k in rounds:
+        rec = {"kernel": k, "B": B, "T": T, "S": S, "V": V, "M": M, "n_iter": n_iter, "ms": t[k] * 1e3,
+               "pairs_ms": [r * 1e3 for r in rounds[k]], "us_per_member_iteration": t[k] * 1e6 / (M * n_iter)}
+        if k == "sequential_fit":
+            rec["x_ensemble_fit"] = t[k] / t["ensemble_fit"]
+            rec["ensemble_faster_in_every_pair"] = all(o > f for o, f in zip(rounds[k], rounds["ensemble_fit"]))
         print(json.dumps(rec))
 
 
@@ -511,9 +612,12 @@ if __name__ == "__main__":
     ap.add_argument("--K", type=int, default=32)
     ap.add_argument("--V", type=int, default=512)
     ap.add_argument("--N", type=int, default=64)
+    ap.add_argument("--M", type=int, default=8)
+    ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--old-route", action="store_true")
     a = ap.parse_args()
     {"vq": bench_vq, "stream": bench_stream, "viterbi": bench_viterbi, "fwdbwd": bench_fwdbwd,
-     "filter": bench_filter, "xi": bench_xi, "estep": bench_estep, "code_viterbi": bench_code_viterbi,
+     "filter": bench_filter, "xi": bench_xi, "estep": bench_estep, "estep_batched": bench_estep_batched,
+     "code_fit": bench_code_fit, "code_viterbi": bench_code_viterbi,
      "code_filter": bench_code_filter, "sample": bench_sample, "vq_stats": bench_vq_stats,
      "vq_bwd": bench_vq_bwd}[a.what](a)

@@ -401,6 +401,24 @@ int vqhmm_code_estep_f32(const float* log_pi, const float* log_A, const float* l
                                gamma, ws, (hipStream_t)stream);
 }
 
+size_t vqhmm_code_estep_batched_workspace_size(int64_t B, int64_t T, int64_t S, int64_t V, int64_t M) {
+  return hmm_code_estep_batched_ws_bytes(B, T, S, V, M);
+}
+
+int vqhmm_code_estep_batched_f32(const float* log_pi, const float* log_A, const float* log_B, const int32_t* codes,
+                                 const int64_t* lengths, const float* weights, int64_t B, int64_t T, int64_t S,
+                                 int64_t V, int64_t M, double* pi_cnt, double* trans_cnt, double* emit_cnt,
+                                 float* loglik, float* gamma, void* ws, size_t ws_bytes, void* stream) {
+  if (B < 0 || T < 0 || S < 1 || V < 1 || M < 0) return VQHMM_EINVAL;
+  if (!hmm_code_supported(S, V) || !hmm_code_members_supported(M)) return VQHMM_EUNSUPPORTED;
+  if (!log_pi || !log_A || !log_B || !pi_cnt || !trans_cnt || !emit_cnt || (B > 0 && !lengths) ||
+      (B * T > 0 && !codes))
+    return VQHMM_EINVAL;
+  if (B * T > 0 && (!ws || ws_bytes < hmm_code_estep_batched_ws_bytes(B, T, S, V, M))) return VQHMM_EWORKSPACE;
+  return launch_hmm_code_estep_batched(log_pi, log_A, log_B, codes, lengths, weights, B, T, S, V, M, pi_cnt, trans_cnt,
+                                       emit_cnt, loglik, gamma, ws, (hipStream_t)stream);
+}
+
 int vqhmm_code_sample_f32(const float* log_pi, const float* log_A, const float* log_B, const float* uniforms,
                           int64_t N, int64_t T, int64_t S, int64_t V, int32_t* states, int32_t* codes, void* stream) {
   if (N < 0 || T < 0 || S < 1 || V < 1 || !log_pi || !log_A || !log_B ||

@@ -36,6 +36,14 @@
 // the grid), a workgroup sums its waves' slabs in wave order into its partial (workspace), and a second
 // launch sums the partials in fp64 in a fixed order (code_reduce_kernel): the same bits run to run.
 //
+// Members.  blockIdx.y is the member of a stack of M models that share codes and lengths (the batched
+// entry; the single-model entry is M = 1): a member has its own parameter slices, exp(log_B)^T table, x rows,
+// partials and outputs, `mstride` workspace bytes and one output block after the previous member's, and runs
+// exactly the single model's plan, so its bits are the single-model call's.  Sequence b enters member m's counts
+// with the weight w[m, b] (1 without weights): one fp64 fma where a contribution is already added in fp64 (the
+// slab bin, the per-chunk flush of the transition registers, the t = 0 posterior), so w = 1 keeps the
+// unweighted bits.  Member and weight are wave-uniform (blockIdx.y, and a load at the wave's own b).
+//
 // Addressing.  codes are read at min(t, T - 1) of the wave's own row, parameters only at (i, j) < S and
 // validated codes, the workspace only inside its own sequence's rows.
 #include "hmm_code_dev.h"  // the lane helpers, the fast step's range and the exp(log_B)^T prologue
@@ -57,25 +65,33 @@ struct CodeArgs {
   const int64_t* lengths;
   int64_t B;
   int T, S, V;
+  const float* weights;  // (M, B), nullable (= all 1)
   const float* Bt;  // (V, S) exp(log_B)^T
   float* alpha;     // (B, T, S) x_t
   double* part;     // [gridDim.x][V*S (v-major) + S*S + S]
   float* loglik;    // nullable
   float* gamma;     // nullable
+  size_t mstride;   // bytes from a member's Bt / alpha / part to the next member's
 };
 
 // out = sum over the partials, in a fixed order: 16 elements per workgroup, thread (py, kx) adds partials
 // py, py + 16, .. of element kx in index order (16 independent loads in flight per element instead of one
 // serial walk), then the 16 sums are added in py order; the emission block leaves transposed to (S, V)
 constexpr int CE_RK = 16, CE_RP = 16;
-__global__ __launch_bounds__(CE_RK * CE_RP) void code_reduce_kernel(const double* __restrict__ part, int np, int S,
-                                                                    int V, double* __restrict__ pi_cnt,
+__global__ __launch_bounds__(CE_RK * CE_RP) void code_reduce_kernel(const double* __restrict__ part, size_t mstride,
+                                                                    int np, int S, int V,
+                                                                    double* __restrict__ pi_cnt,
                                                                     double* __restrict__ trans_cnt,
                                                                     double* __restrict__ emit_cnt) {
   __shared__ double red[CE_RP][CE_RK];
   const int64_t NV = (int64_t)S * V, NE = NV + (int64_t)S * S + S;
   const int kx = threadIdx.x % CE_RK, py = threadIdx.x / CE_RK;
   const int64_t k = (int64_t)blockIdx.x * CE_RK + kx;
+  const int64_t mem = blockIdx.y;  // member: its own partials (mstride bytes apart) and output blocks
+  part = reinterpret_cast<const double*>(reinterpret_cast<const char*>(part) + mem * mstride);
+  pi_cnt += mem * S;
+  trans_cnt += mem * S * S;
+  emit_cnt += mem * NV;
   double acc = 0.0;
   if (k < NE) {
 #pragma unroll 4
@@ -97,9 +113,28 @@ __global__ __launch_bounds__(CE_RK * CE_RP) void code_reduce_kernel(const double
   }
 }
 
-template <int SP, bool LDS_T>
-__global__ __launch_bounds__(256) void code_estep_kernel(const CodeArgs a) {
+// member m's view of the arguments (m = 0 changes nothing)
+__device__ __forceinline__ CodeArgs code_member(CodeArgs a, int64_t m) {
+  a.log_pi += m * a.S;
+  a.log_A += m * a.S * a.S;
+  a.log_B += m * (int64_t)a.S * a.V;
+  if (a.weights) a.weights += m * a.B;
+  a.Bt = reinterpret_cast<const float*>(reinterpret_cast<const char*>(a.Bt) + m * a.mstride);
+  a.alpha = reinterpret_cast<float*>(reinterpret_cast<char*>(a.alpha) + m * a.mstride);
+  a.part = reinterpret_cast<double*>(reinterpret_cast<char*>(a.part) + m * a.mstride);
+  if (a.loglik) a.loglik += m * a.B;
+  if (a.gamma) a.gamma += m * a.B * (int64_t)a.T * a.S;
+  return a;
+}
+
+// WT: the call has weights.  Without them the weight is the constant 1 and every weighted add below is the plain
+// fp64 add again, at no cost in registers.  MEM: the launch has more than one member.  With one, the arguments
+// stay kernel arguments: offset pointers are computed values that the register allocator has to keep (at SP = 32
+// in spilled scalar registers, measured at 1 % of the single-model call, profiles/code_ensemble).
+template <int SP, bool LDS_T, bool WT, bool MEM>
+__global__ __launch_bounds__(256) void code_estep_kernel(const CodeArgs a0) {
   extern __shared__ double ce_smem[];
+  const CodeArgs a = MEM ? code_member(a0, blockIdx.y) : a0;
   const int S = a.S, V = a.V, T = a.T;
   const int NV = S * V, NT = S * S + S;
   const int tid = threadIdx.x, lane = tid & 63;
@@ -253,6 +288,7 @@ __global__ __launch_bounds__(256) void code_estep_kernel(const CodeArgs a) {
       continue;
     }
     if (a.loglik && lane == 0) a.loglik[b] = (float)Sll;
+    const double wt = WT ? (double)ce_uni(a.weights[b]) : 1.0;  // the sequence's weight in every count
     __threadfence();  // the staging loads below read rows other lanes of this wave stored
 
     // ----------------------------------------------------------------- backward
@@ -268,9 +304,10 @@ __global__ __launch_bounds__(256) void code_estep_kernel(const CodeArgs a) {
         // t = L - 1: gamma = x_{L-1}
         const int code = ce_uni(cb[L - 1]);
         if (act) {
-          slab[(int64_t)code * S + j] += (double)x;
+          double* bin = slab + ((int64_t)code * S + j);
+          *bin = fma(wt, (double)x, *bin);
           if (gm_out) gm_out[(int64_t)(L - 1) * S + j] = x;
-          if (L == 1) pc64 += (double)x;
+          if (L == 1) pc64 = fma(wt, (double)x, pc64);
         }
       }
       for (int t0 = ((L - 1) / CE_CH) * CE_CH; t0 >= 0; t0 -= CE_CH) {
@@ -373,14 +410,14 @@ __global__ __launch_bounds__(256) void code_estep_kernel(const CodeArgs a) {
             }
           }
           if (act) {
-            *bin = bin0 + (double)gm;
+            *bin = fma(wt, (double)gm, bin0);
             if (gm_out) gm_out[(int64_t)(t - 1) * S + j] = gm;
-            if (t == 1) pc64 += (double)gm;
+            if (t == 1) pc64 = fma(wt, (double)gm, pc64);
           }
         }
 #pragma unroll
         for (int q = 0; q < SP; ++q) {
-          tc64[q] += (double)tc[q];
+          tc64[q] = fma(wt, (double)tc[q], tc64[q]);
           tc[q] = 0.f;
         }
       }
@@ -487,67 +524,93 @@ CodePlan code_plan(int64_t B, int64_t T, int64_t S, int64_t V) {
   return p;
 }
 
-template <int SP>
-int estep_go(const CodeArgs& a, const CodePlan& p, hipStream_t s) {
+template <int SP, bool WT, bool MEM>
+int estep_go(const CodeArgs& a, const CodePlan& p, int64_t M, hipStream_t s) {
+  const dim3 grid((unsigned)p.nblk, (unsigned)M);
   if (p.lds) {
-    auto kern = code_estep_kernel<SP, true>;
+    auto kern = code_estep_kernel<SP, true, WT, MEM>;
     // more than 64 KB of dynamic LDS has to be asked for, once per kernel (the tier's limit covers every launch)
     static const hipError_t big_lds = hipFuncSetAttribute(
         reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)CE_LDS_MAX);
     (void)big_lds;
-    kern<<<(unsigned)p.nblk, 64 * p.nw, p.lds_bytes, s>>>(a);
+    kern<<<grid, 64 * p.nw, p.lds_bytes, s>>>(a);
   } else {
-    code_estep_kernel<SP, false><<<(unsigned)p.nblk, 64, p.lds_bytes, s>>>(a);
+    code_estep_kernel<SP, false, WT, MEM><<<grid, 64, p.lds_bytes, s>>>(a);
   }
   VQHMM_LAUNCH_CHECK();
   return VQHMM_OK;
 }
 
+template <bool WT, bool MEM>
+int estep_width(const CodeArgs& a, const CodePlan& p, int64_t M, hipStream_t s) {
+  if (a.S > 16) return estep_go<32, WT, MEM>(a, p, M, s);
+  if (a.S > 8) return estep_go<16, WT, MEM>(a, p, M, s);
+  if (a.S > 4) return estep_go<8, WT, MEM>(a, p, M, s);
+  if (a.S > 2) return estep_go<4, WT, MEM>(a, p, M, s);
+  if (a.S > 1) return estep_go<2, WT, MEM>(a, p, M, s);
+  return estep_go<1, WT, MEM>(a, p, M, s);
+}
+
 }  // namespace
 
 bool hmm_code_supported(int64_t S, int64_t V) { return S >= 1 && S <= 32 && V >= 1 && V <= 65536; }
+bool hmm_code_members_supported(int64_t M) { return M >= 1 && M <= 65535; }  // the member axis is gridDim.y
 
 size_t hmm_code_estep_ws_bytes(int64_t B, int64_t T, int64_t S, int64_t V) {
   if (!hmm_code_supported(S, V) || B < 0 || T < 0) return 0;
   return code_plan(B, T, S, V).bytes;
 }
 
+// M members: M single-model workspaces, each rounded up to 256 bytes
+size_t hmm_code_estep_batched_ws_bytes(int64_t B, int64_t T, int64_t S, int64_t V, int64_t M) {
+  if (!hmm_code_supported(S, V) || !hmm_code_members_supported(M) || B < 0 || T < 0) return 0;
+  return (size_t)M * r256(code_plan(B, T, S, V).bytes);
+}
+
 int launch_hmm_code_estep(const float* log_pi, const float* log_A, const float* log_B, const int32_t* codes,
                           const int64_t* lengths, int64_t B, int64_t T, int64_t S, int64_t V, double* pi_cnt,
                           double* trans_cnt, double* emit_cnt, float* loglik, float* gamma, void* ws, hipStream_t s) {
-  if (!hmm_code_supported(S, V) || T > (1 << 28) || B > INT32_MAX) return VQHMM_EUNSUPPORTED;
+  return launch_hmm_code_estep_batched(log_pi, log_A, log_B, codes, lengths, nullptr, B, T, S, V, 1, pi_cnt,
+                                       trans_cnt, emit_cnt, loglik, gamma, ws, s);
+}
+
+int launch_hmm_code_estep_batched(const float* log_pi, const float* log_A, const float* log_B, const int32_t* codes,
+                                  const int64_t* lengths, const float* weights, int64_t B, int64_t T, int64_t S,
+                                  int64_t V, int64_t M, double* pi_cnt, double* trans_cnt, double* emit_cnt,
+                                  float* loglik, float* gamma, void* ws, hipStream_t s) {
+  if (!hmm_code_supported(S, V) || !hmm_code_members_supported(M) || T > (1 << 28) || B > INT32_MAX)
+    return VQHMM_EUNSUPPORTED;
   if (B == 0 || T == 0) {
-    if (hipMemsetAsync(pi_cnt, 0, sizeof(double) * S, s) != hipSuccess ||
-        hipMemsetAsync(trans_cnt, 0, sizeof(double) * S * S, s) != hipSuccess ||
-        hipMemsetAsync(emit_cnt, 0, sizeof(double) * S * V, s) != hipSuccess)
+    if (hipMemsetAsync(pi_cnt, 0, sizeof(double) * M * S, s) != hipSuccess ||
+        hipMemsetAsync(trans_cnt, 0, sizeof(double) * M * S * S, s) != hipSuccess ||
+        hipMemsetAsync(emit_cnt, 0, sizeof(double) * M * S * V, s) != hipSuccess)
       return VQHMM_ELAUNCH;
     // length-0 sequences: loglik = NaN (all-ones words)
-    if (B > 0 && loglik && hipMemsetAsync(loglik, 0xFF, sizeof(float) * B, s) != hipSuccess) return VQHMM_ELAUNCH;
+    if (B > 0 && loglik && hipMemsetAsync(loglik, 0xFF, sizeof(float) * M * B, s) != hipSuccess)
+      return VQHMM_ELAUNCH;
     return VQHMM_OK;
   }
   const CodePlan p = code_plan(B, T, S, V);
   char* w = static_cast<char*>(ws);
   CodeArgs a;
   a.log_pi = log_pi; a.log_A = log_A; a.log_B = log_B; a.codes = codes; a.lengths = lengths;
+  a.weights = weights;
   a.B = B; a.T = (int)T; a.S = (int)S; a.V = (int)V;
   a.alpha = reinterpret_cast<float*>(w);
   float* Bt = reinterpret_cast<float*>(w + p.off_bt);
   a.Bt = Bt;
   a.part = reinterpret_cast<double*>(w + p.off_part);
   a.loglik = loglik; a.gamma = gamma;
-  code_bt_kernel<<<(unsigned)cdiv(S * V, 256), 256, 0, s>>>(log_B, (int)S, (int)V, Bt);
+  a.mstride = r256(p.bytes);
+  code_bt_kernel<<<dim3((unsigned)cdiv(S * V, 256), (unsigned)M), 256, 0, s>>>(log_B, (int)S, (int)V, Bt, S * V,
+                                                                               (int64_t)(a.mstride / 4));
   VQHMM_LAUNCH_CHECK();
-  int rc;
-  if (S > 16) rc = estep_go<32>(a, p, s);
-  else if (S > 8) rc = estep_go<16>(a, p, s);
-  else if (S > 4) rc = estep_go<8>(a, p, s);
-  else if (S > 2) rc = estep_go<4>(a, p, s);
-  else if (S > 1) rc = estep_go<2>(a, p, s);
-  else rc = estep_go<1>(a, p, s);
+  const int rc = weights ? (M > 1 ? estep_width<true, true>(a, p, M, s) : estep_width<true, false>(a, p, M, s))
+                         : (M > 1 ? estep_width<false, true>(a, p, M, s) : estep_width<false, false>(a, p, M, s));
   if (rc) return rc;
   const int64_t NE = S * V + S * S + S;
-  code_reduce_kernel<<<(unsigned)cdiv(NE, CE_RK), CE_RK * CE_RP, 0, s>>>(a.part, (int)p.nblk, (int)S, (int)V, pi_cnt, trans_cnt,
-                                                            emit_cnt);
+  code_reduce_kernel<<<dim3((unsigned)cdiv(NE, CE_RK), (unsigned)M), CE_RK * CE_RP, 0, s>>>(
+      a.part, a.mstride, (int)p.nblk, (int)S, (int)V, pi_cnt, trans_cnt, emit_cnt);
   VQHMM_LAUNCH_CHECK();
   return VQHMM_OK;
 }

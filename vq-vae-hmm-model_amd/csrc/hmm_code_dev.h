@@ -45,10 +45,15 @@ __device__ __forceinline__ float ce_red(float v, Op op) {
   return v;
 }
 
+// blockIdx.y = the member of a stack of models (hmm_code.hip's batched E-step): its log_B lies lb_stride floats
+// and its table bt_stride floats after the previous member's
 __global__ __launch_bounds__(256) void code_bt_kernel(const float* __restrict__ log_B, int S, int V,
-                                                      float* __restrict__ Bt) {
+                                                      float* __restrict__ Bt, int64_t lb_stride = 0,
+                                                      int64_t bt_stride = 0) {
   const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (k >= (int64_t)S * V) return;
+  log_B += blockIdx.y * lb_stride;
+  Bt += blockIdx.y * bt_stride;
   const int v = (int)(k / S), s = (int)(k - (int64_t)v * S);
   Bt[k] = __expf(log_B[(int64_t)s * V + v]);
 }

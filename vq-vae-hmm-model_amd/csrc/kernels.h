@@ -514,6 +514,14 @@ size_t hmm_code_estep_ws_bytes(int64_t B, int64_t T, int64_t S, int64_t V);
 int launch_hmm_code_estep(const float* log_pi, const float* log_A, const float* log_B, const int32_t* codes,
                           const int64_t* lengths, int64_t B, int64_t T, int64_t S, int64_t V, double* pi_cnt,
                           double* trans_cnt, double* emit_cnt, float* loglik, float* gamma, void* ws, hipStream_t s);
+// ... the same kernel on a stack of 1 <= M <= 65535 models that share codes and lengths: every parameter and
+// output gains a leading member axis, weights (M,B) nullable (= 1) scale each sequence's counts per member
+bool hmm_code_members_supported(int64_t M);
+size_t hmm_code_estep_batched_ws_bytes(int64_t B, int64_t T, int64_t S, int64_t V, int64_t M);
+int launch_hmm_code_estep_batched(const float* log_pi, const float* log_A, const float* log_B, const int32_t* codes,
+                                  const int64_t* lengths, const float* weights, int64_t B, int64_t T, int64_t S,
+                                  int64_t V, int64_t M, double* pi_cnt, double* trans_cnt, double* emit_cnt,
+                                  float* loglik, float* gamma, void* ws, hipStream_t s);
 int launch_hmm_code_sample(const float* log_pi, const float* log_A, const float* log_B, const float* uniforms,
                            int64_t N, int64_t T, int64_t S, int64_t V, int32_t* states, int32_t* codes,
                            hipStream_t s);

@@ -55,6 +55,9 @@ _SIGS = {
     "vqhmm_code_estep_workspace_size": (c_sz, [c_i64, c_i64, c_i64, c_i64]),
     "vqhmm_code_estep_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp,
                                             c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "vqhmm_code_estep_batched_workspace_size": (c_sz, [c_i64, c_i64, c_i64, c_i64, c_i64]),
+    "vqhmm_code_estep_batched_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64,
+                                                    c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "vqhmm_code_sample_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp]),
     "vqhmm_code_viterbi_workspace_size": (c_sz, [c_i64, c_i64, c_i64, c_i64]),
     "vqhmm_code_viterbi_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp,

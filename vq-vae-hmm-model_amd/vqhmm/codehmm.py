@@ -3,7 +3,9 @@ streaming causal filter (pseudocode.txt:25-32: `hmm.train_em(all_code_indices)`,
 math.md:23-62 with M_t = M).  HIP only: the E-step and the sampler are the fused kernels of hmm_code.hip
 (vqhmm_code_estep_f32 / vqhmm_code_sample_f32), decode and filter those of hmm_code_decode.hip
 (vqhmm_code_viterbi_f32 / vqhmm_code_filter_f32), contracts in include/vqhmm.h; the M-step is
-S*S + S*V numbers of torch arithmetic in fp64 on the device.
+S*S + S*V numbers of torch arithmetic in fp64 on the device.  `code_log_prob` is the differentiable
+log-likelihood (its backward is one weighted E-step); restarts (`fit(n_init=R)`) run on
+codehmm_ensemble.CodeHMMEnsemble, R models in one launch (vqhmm_code_estep_batched_f32).
 """
 import torch
 
@@ -15,6 +17,94 @@ MAX_CODES = 65536
 
 def _row_log_normalise(w):
     return torch.log(w / w.sum(-1, keepdim=True)).float()
+
+
+def _check_codes(what, ref, codes, lengths):
+    """codes (B,T) int32/int64 and lengths (B,) or None on ref's device -> (int32 codes, int64 lengths, B, T)."""
+    _ext.require_device(ref, codes)
+    if codes.dim() != 2 or codes.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"{what}: expected codes (B, T) int32 or int64, got {tuple(codes.shape)} {codes.dtype}")
+    codes = codes.to(torch.int32).contiguous()
+    B, T = codes.shape
+    if lengths is None:
+        lengths = torch.full((B,), T, dtype=torch.int64, device=codes.device)
+    lengths = torch.as_tensor(lengths).to(codes.device, torch.int64).contiguous()
+    if lengths.shape != (B,):
+        raise ValueError(f"{what}: lengths must have shape ({B},)")
+    return codes, lengths, B, T
+
+
+def _estep_batched(what, log_pi, log_A, log_B, codes, lengths, weights, want_loglik, want_gamma,
+                   max_workspace_bytes=None):
+    """vqhmm_code_estep_batched_f32 on stacked contiguous fp32 parameters (M,S) / (M,S,S) / (M,S,V), int32
+    codes (B,T), int64 lengths (B) and weights (M,B) fp32 or None -> (pi_cnt (M,S), trans_cnt (M,S,S), emit_cnt
+    (M,S,V) fp64, loglik (M,B) or None, gamma (M,B,T,S) or None).  The members run in groups whose workspace fits
+    max_workspace_bytes (None: one group); a member's bits do not depend on its group."""
+    M, S = log_pi.shape
+    V = log_B.shape[-1]
+    B, T = codes.shape
+    dev = codes.device
+    pi = torch.empty((M, S), dtype=torch.float64, device=dev)
+    tr = torch.empty((M, S, S), dtype=torch.float64, device=dev)
+    em = torch.empty((M, S, V), dtype=torch.float64, device=dev)
+    ll = torch.empty((M, B), dtype=torch.float32, device=dev) if want_loglik else None
+    gm = torch.empty((M, B, T, S), dtype=torch.float32, device=dev) if want_gamma else None
+    lib = _ext.load()
+    G = min(M, 65535)
+    if max_workspace_bytes is not None:
+        per = lib.vqhmm_code_estep_batched_workspace_size(B, T, S, V, 1)
+        G = max(1, min(G, int(max_workspace_bytes) // max(per, 1)))
+    nb = lib.vqhmm_code_estep_batched_workspace_size(B, T, S, V, G)
+    ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=dev)
+    st = _ext.stream_ptr(dev)
+
+    def at(t, m0):
+        return _ext.ptr(t[m0:]) if t is not None else _ext.ptr(None)
+
+    with torch.no_grad():
+        for m0 in range(0, M, G):
+            _ext.check(lib.vqhmm_code_estep_batched_f32(
+                at(log_pi, m0), at(log_A, m0), at(log_B, m0), _ext.ptr(codes), _ext.ptr(lengths), at(weights, m0),
+                B, T, S, V, min(G, M - m0), at(pi, m0), at(tr, m0), at(em, m0), at(ll, m0), at(gm, m0),
+                _ext.ptr(ws), nb, st), what)
+    return pi, tr, em, ll, gm
+
+
+class _CodeLogProb(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, log_pi, log_A, log_B, codes, lengths):
+        ll = _estep_batched("code_log_prob", log_pi[None], log_A[None], log_B[None], codes, lengths, None, True,
+                            False)[3][0]
+        ctx.save_for_backward(log_pi, log_A, log_B, codes, lengths)
+        return ll
+
+    @staticmethod
+    def backward(ctx, g):
+        log_pi, log_A, log_B, codes, lengths = ctx.saved_tensors
+        w = g.detach().to(torch.float32).reshape(1, -1).contiguous()
+        pi, tr, em, _, _ = _estep_batched("code_log_prob backward", log_pi[None], log_A[None], log_B[None], codes,
+                                          lengths, w, False, False)
+        return pi[0].float(), tr[0].float(), em[0].float(), None, None
+
+
+def code_log_prob(log_pi, log_A, log_B, codes, lengths=None):
+    """log p(codes[b, :lengths[b]]) (B,) fp32 under the HMM (log_pi (S,), log_A (S,S), log_B (S,V), fp32 device
+    tensors), differentiable with respect to the three log-parameter tensors treated as free variables: train
+    logits through log_softmax and autograd chains it.  The forward is the fused E-step's loglik; the backward is
+    one weighted E-step with weights = grad_output, whose counts (fp64, cast to fp32) are the gradients:
+    d loglik_b / d log_pi = gamma_{b,0}, / d log_A = sum_t xi_{b,t}, / d log_B[s,v] = sum_{codes=v} gamma_{b,t}(s).
+    A sequence whose loglik is not finite (length 0 -> NaN, a code outside [0, V) -> NaN, impossible -> -inf)
+    contributes exactly zero gradient, not the NaN a logsumexp recursion in torch would give.  grad_output must be
+    finite."""
+    S, V = int(log_B.shape[0]), int(log_B.shape[-1])
+    for name, t, shape in (("log_pi", log_pi, (S,)), ("log_A", log_A, (S, S)), ("log_B", log_B, (S, V))):
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or tuple(t.shape) != shape:
+            raise ValueError(f"code_log_prob: {name} must be a float32 tensor of shape {shape}")
+    if not (1 <= S <= MAX_STATES and 1 <= V <= MAX_CODES):
+        raise ValueError(f"code_log_prob: 1 <= S <= {MAX_STATES} and 1 <= V <= {MAX_CODES} (got {S}, {V})")
+    _ext.require_device(log_pi, log_A, log_B)
+    codes, lengths, _, _ = _check_codes("code_log_prob", log_pi, codes, lengths)
+    return _CodeLogProb.apply(log_pi.contiguous(), log_A.contiguous(), log_B.contiguous(), codes, lengths)
 
 
 class CodeHMM(torch.nn.Module):
@@ -41,17 +131,7 @@ class CodeHMM(torch.nn.Module):
 
     # ------------------------------------------------------------------ inputs
     def _inputs(self, codes, lengths):
-        _ext.require_device(self.log_pi, codes)
-        if codes.dim() != 2 or codes.dtype not in (torch.int32, torch.int64):
-            raise ValueError(f"CodeHMM: expected codes (B, T) int32 or int64, got {tuple(codes.shape)} {codes.dtype}")
-        codes = codes.to(torch.int32).contiguous()
-        B, T = codes.shape
-        if lengths is None:
-            lengths = torch.full((B,), T, dtype=torch.int64, device=codes.device)
-        lengths = torch.as_tensor(lengths).to(codes.device, torch.int64).contiguous()
-        if lengths.shape != (B,):
-            raise ValueError(f"CodeHMM: lengths must have shape ({B},)")
-        return codes, lengths, B, T
+        return _check_codes("CodeHMM", self.log_pi, codes, lengths)
 
     def _estep(self, codes, lengths, B, T, want_loglik, want_gamma):
         S, V = self.num_states, self.num_codes
@@ -180,10 +260,46 @@ class CodeHMM(torch.nn.Module):
         self.log_A.copy_(self._m_rows(counts["trans_cnt"], self.log_A, prior_count))
         self.log_B.copy_(self._m_rows(counts["emit_cnt"], self.log_B, prior_count))
 
-    def fit(self, codes, lengths=None, n_iter=20, tol=None, prior_count=0.0):
+    def _restart_ensemble(self, n_init, generator=None):
+        """The starts of fit(n_init=R): member 0 = the current parameters, members 1..R-1 = CodeHMM(S, V, generator)
+        drawn in that order, each with this model's structural zeros imposed and its rows renormalised."""
+        from .codehmm_ensemble import CodeHMMEnsemble
+        S, V = self.num_states, self.num_codes
+        dev = self.log_pi.device
+        starts = [self]
+        for _ in range(int(n_init) - 1):
+            h = CodeHMM(S, V, generator=generator).to(dev)
+            for k in ("log_pi", "log_A", "log_B"):
+                new = torch.where(getattr(self, k) != float("-inf"), getattr(h, k).double(), float("-inf"))
+                lse = torch.logsumexp(new, -1, keepdim=True)
+                getattr(h, k).copy_(torch.where(lse != float("-inf"), new - lse, new).float())
+            starts.append(h)
+        return CodeHMMEnsemble.from_models(starts)
+
+    def fit(self, codes, lengths=None, n_iter=20, tol=None, prior_count=0.0, n_init=1, generator=None):
         """Baum-Welch: alternate e_step and m_step.  Returns the total log-likelihoods, one per iteration, each
         under the parameters before that iteration's M-step (0-dim device tensors with tol=None, so the loop
-        has no host sync; floats with tol, which stops once the improvement per observed position is < tol)."""
+        has no host sync; floats with tol, which stops once the improvement per observed position is < tol).
+
+        n_init = R > 1: R chains in one batched E-step per iteration (CodeHMMEnsemble): member 0 starts from the
+        current parameters, members 1..R-1 from fresh random starts drawn from `generator`, all with the current
+        structural zeros.  The member with the largest total log-likelihood under its final parameters (one
+        more batched E-step) is copied into this model, selected on the device; the history returned is that
+        member's.  No host sync; `tol` cannot be combined with it."""
+        n_init = int(n_init)
+        if n_init < 1:
+            raise ValueError("CodeHMM.fit: n_init >= 1")
+        if n_init > 1:
+            if tol is not None:
+                raise ValueError("CodeHMM.fit: tol needs a host sync per iteration and cannot be combined with n_init > 1")
+            codes, lengths, B, T = self._inputs(codes, lengths)
+            ens = self._restart_ensemble(n_init, generator)
+            hist = ens.fit(codes, lengths, n_iter=n_iter, prior_count=prior_count)
+            best = ens.best_index(codes, lengths)
+            with torch.no_grad():
+                for k in ("log_pi", "log_A", "log_B"):
+                    getattr(self, k).copy_(getattr(ens, k).index_select(0, best)[0])
+            return list(hist.index_select(1, best)[:, 0].unbind(0))
         codes, lengths, B, T = self._inputs(codes, lengths)
         npos = None
         history = []
