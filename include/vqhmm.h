@@ -315,6 +315,77 @@ int vqhmm_code_sample_f32(const float* log_pi, const float* log_A, const float* 
                           const float* uniforms, int64_t N, int64_t T, int64_t S, int64_t V,
                           int32_t* states, int32_t* codes, void* stream);
 
+/* ------------------------------------- Gaussian HMM on continuous data ----
+ * The stationary HMM with diagonal-Gaussian emissions (hmm_gauss.hip): log_pi (S), log_A (S,S) with
+ * log_A[i,j] = log p(z_t = j | z_{t-1} = i), mean (S,D), log_var (S,D), all fp32; rows of log_pi and
+ * log_A need not be normalised and -inf there is a structural zero.  1 <= S <= 32, 1 <= D <= 64 (else
+ * VQHMM_EUNSUPPORTED, and the workspace query returns 0).  x (B,T,D) fp32 row-major, lengths (B) int64
+ * clamped to [0, T]; x at t >= length is never interpreted.
+ *
+ * vqhmm_gauss_emission_f32: em (B,T,S) fp32,
+ *   em[b,t,s] = -1/2 sum_d ((x_d - mean_sd)^2 exp(-log_var_sd) + log_var_sd) - (D/2) ln 2 pi
+ * computed as fma(-1/2, q, c_s): q the fp32 running sum over d in index order of fma((x_d - mean_sd)^2,
+ * expf(-log_var_sd), q), c_s = -1/2 sum_d log_var_sd - (D/2) ln 2 pi summed in fp64 and rounded once.
+ * Rows at t >= length are -inf; every element is written.  Accuracy target vs fp64 on the same fp32
+ * inputs: (D + 16) 2^-23 (sum_d (z^2/2 + |log_var|/2) + (D/2) ln 2 pi).  No workspace.
+ *
+ * vqhmm_gauss_estep_f32: the Baum-Welch E-step in one call (two launches).  Every element of
+ *   pi_cnt (S)      = sum_b w_b gamma_{b,0}(s)
+ *   trans_cnt (S,S) = sum_b w_b sum_{1 <= t < L_b} xi_{b,t}(i,j)
+ *   occ (S)         = sum_b w_b sum_{t < L_b} gamma_{b,t}(s)
+ *   m1 (S,D)        = sum_b w_b sum_{t < L_b} gamma_{b,t}(s) (x_{b,t,d} - shift_d)
+ *   m2 (S,D)        = sum_b w_b sum_{t < L_b} gamma_{b,t}(s) (x_{b,t,d} - shift_d)^2
+ * is written, in fp64 (the caller never clears them).  shift (D) fp32 is nullable (= 0): moments about
+ * a point near the data keep the M-step's variance from being a difference of two huge numbers.
+ * weights (B) fp32 is nullable (w_b = 1): the product is one fp64 fma where the contribution is added
+ * in fp64, so all-ones weights give the bits of weights = NULL; weights may be negative or 0 and must
+ * be finite.  loglik (B) fp32 = log p(x_{b,0:L_b}) and gamma (B,T,S) fp32 (rows at t >= L are 0) are
+ * nullable and do not depend on the weights; with gamma NULL nothing of size B*T*S is written as
+ * output.  The emissions the chain uses are, bit for bit, what vqhmm_gauss_emission_f32 writes; they
+ * are recomputed on chip from x in both passes (each step uses exp(em_t - max_s em_t), the maxima go
+ * into the fp64 log-likelihood sum) and neither they nor xi reach memory.  The chain is
+ * vqhmm_code_estep_f32's: linear probabilities normalised at every step, the transition matrix in
+ * registers, a step whose mass leaves [2^-30, 2^30] redone max-shifted in natural log.  Length 0:
+ * loglik = NaN.  An impossible sequence (mass truly 0): loglik = -inf.  A non-finite x or emission
+ * inside the length: loglik = NaN.  All three contribute exactly 0 to every count, have zero gamma
+ * rows and leave the other sequences untouched.  Deterministic (static assignment of sequences to
+ * waves, private slabs, a fixed-order fp64 reduction launch, no float atomics), graph-capturable, no
+ * host sync, 64-bit offsets, every global access inside its own array (exact-size allocations and
+ * pointers misaligned by 4 bytes are safe).  Workspace: vqhmm_gauss_estep_workspace_size(B, T, S, D)
+ * bytes (the scaled forward vectors, 4*S bytes per position, and the partial sums).
+ * Accuracy target vs the fp64 oracle fed the same emissions, per position: |gamma| abs 1e-5, |xi| abs
+ * 2e-5, loglik rel 1e-5 of max(1, |loglik|); m1 and m2 2e-5 of sum |x - shift| and sum (x - shift)^2.
+ *
+ * vqhmm_gauss_sample_f32: ancestral sampling of N sequences of length T.  uniforms (N,T) fp32 in
+ * [0,1) draw z_t by vqhmm_code_sample_f32's inverse-CDF rule (from pi at t = 0, from row z_{t-1} of A
+ * afterwards); x[n,t,d] = fmaf(sd, normals[n,t,d], mean[z_t,d]) with sd = exp(log_var[z_t,d] / 2)
+ * taken in fp64 and rounded once, normals (N,T,D) fp32 caller-supplied.  states (N,T) int32, x (N,T,D)
+ * fp32.  Bit-reproducible given the draws.  No workspace.
+ *
+ * Return codes, checked in this order on the host before any launch: a negative size ->
+ * VQHMM_EINVAL; S or D out of range -> VQHMM_EUNSUPPORTED (as are T > 2^28, B >= 2^31 and B*T > 2^40, for
+ * which the workspace query returns 0 too); B*T == 0 (N*T == 0) -> VQHMM_OK without a
+ * launch, the E-step's five counts zeroed (they must not be NULL: VQHMM_EINVAL) and loglik = NaN for
+ * B > 0; a null required pointer or a workspace that is too small -> VQHMM_EINVAL. */
+int vqhmm_gauss_emission_f32(const float* mean, const float* log_var,
+                             const float* x, const int64_t* lengths,
+                             int64_t B, int64_t T, int64_t S, int64_t D,
+                             float* em, void* stream);
+size_t vqhmm_gauss_estep_workspace_size(int64_t B, int64_t T, int64_t S, int64_t D);
+int vqhmm_gauss_estep_f32(const float* log_pi, const float* log_A,
+                          const float* mean, const float* log_var,
+                          const float* x, const int64_t* lengths,
+                          const float* shift, const float* weights,
+                          int64_t B, int64_t T, int64_t S, int64_t D,
+                          double* pi_cnt, double* trans_cnt, double* occ, double* m1, double* m2,
+                          float* loglik, float* gamma,
+                          void* workspace, size_t ws_bytes, void* stream);
+int vqhmm_gauss_sample_f32(const float* log_pi, const float* log_A,
+                           const float* mean, const float* log_var,
+                           const float* uniforms, const float* normals,
+                           int64_t N, int64_t T, int64_t S, int64_t D,
+                           int32_t* states, float* x, void* stream);
+
 /* -------------------------------------------------- codebook learning ----
  * Per-code statistics of a batch under given assignments, the quantizer's backward from the same
  * pass, and the channels-first lookup (pseudocode.txt:8-32, the codebook's side; vq_codebook.hip).

@@ -10,6 +10,10 @@
                                                          also M sequential vqhmm_code_estep_f32 calls on the members, in
                                                          five alternating pairs, and a line that checks the two agree
                                                          exactly)
+    python tools/kbench.py gauss_estep --B 2048 --T 200 --K 32 --D 16 [--old-route]
+                                                        (the fused Gaussian-HMM E-step on x (B,T,D); --old-route: also
+                                                         torch emissions + expanded log_A + pairwise_posteriors + torch
+                                                         moment sums, in five alternating pairs, and a check line)
     python tools/kbench.py code_fit --B 256 --T 200 --K 8 --V 512 --M 8 [--iters 20]
                                                         (--iters EM iterations of CodeHMMEnsemble.fit against --M
                                                          sequential CodeHMM.fit(n_init=1) runs, five alternating pairs)
@@ -28,6 +32,7 @@
 """
 import argparse
 import json
+import math
 import os
 import sys
 
@@ -312,6 +317,74 @@ def bench_estep_batched(a):
         if k == "sequential":
             rec["x_estep_batched"] = t[k] / t["estep_batched"]
             rec["batched_faster_in_every_pair"] = all(o > f for o, f in zip(rounds[k], rounds["estep_batched"]))
+        print(json.dumps(rec))
+
+
+def bench_gauss_estep(a):
+    """vqhmm_gauss_estep_f32 (counts + loglik, no gamma) at S = --K states on x (B,T,--D).  --old-route: also the
+    time-varying kernels' way to the same statistics (the emissions in torch, log_A expanded to (B,T,S,S),
+    pairwise_posteriors, the moment sums in torch; all of it inside the timed call, the (B,T,S,S) copy of the
+    expanded view included, which pairwise_posteriors makes itself), in five alternating pairs after a warm-up,
+    every pair's two times reported, and a check line with the largest differences between the two routes' counts relative to the
+    tests' bounds' scales.  Algorithmic HBM bytes per position of the fused call: x read twice (8 D) and the
+    scaled forward vector written and read back (8 S)."""
+    B, T, S, D = a.B, a.T, a.K, a.D
+    g = torch.Generator(device="cuda").manual_seed(11)
+    hmm = vqhmm.GaussianHMM(S, D, generator=torch.Generator().manual_seed(3)).cuda()
+    with torch.no_grad():
+        hmm.mean.mul_(2.0)
+    z = torch.randint(0, S, (B, T), device="cuda", generator=g)
+    x = (hmm.mean[z] + torch.randn((B, T, D), device="cuda", generator=g)).contiguous()
+    L = torch.full((B,), T, dtype=torch.int64, device="cuda")
+    shift = x.mean((0, 1)).contiguous()
+    lib = vqhmm._ext.load()
+    P = vqhmm._ext.ptr
+    st = vqhmm._ext.stream_ptr()
+    names = ("pi_cnt", "trans_cnt", "occ", "m1", "m2")
+    cnt = {k: torch.empty(n, dtype=torch.float64, device="cuda") for k, n in zip(names, (S, S * S, S, S * D, S * D))}
+    ll = torch.empty(B, device="cuda")
+    nb = lib.vqhmm_gauss_estep_workspace_size(B, T, S, D)
+    ws = torch.empty(max(nb, 1), dtype=torch.uint8, device="cuda")
+
+    def new():
+        lib.vqhmm_gauss_estep_f32(P(hmm.log_pi), P(hmm.log_A), P(hmm.mean), P(hmm.log_var), P(x), P(L), P(shift), None,
+                                  B, T, S, D, *(P(cnt[k]) for k in names), P(ll), None, P(ws), nb, st)
+
+    def old():
+        iv = torch.exp(-hmm.log_var)
+        em = -0.5 * (((x[:, :, None, :] - hmm.mean) ** 2 * iv).sum(-1) + hmm.log_var.sum(-1)) - 0.5 * D * math.log(2 * math.pi)
+        gamma, xi, logZ = vqhmm.pairwise_posteriors(hmm.log_pi, hmm.log_A.expand(B, T, S, S), em, L)
+        y = (x - shift).double()
+        gd = gamma.double()
+        return {"pi_cnt": gamma[:, 0].sum(0, dtype=torch.float64), "trans_cnt": xi.sum((0, 1), dtype=torch.float64),
+                "occ": gd.sum((0, 1)), "m1": torch.einsum("bts,btd->sd", gd, y),
+                "m2": torch.einsum("bts,btd->sd", gd, y * y), "loglik": logZ}
+
+    legs = {"gauss_estep": new}
+    if a.old_route:
+        legs["old_route"] = old
+        ref = old()
+        new()
+        torch.cuda.synchronize()
+        n = B * T
+        scale = {"pi_cnt": B, "trans_cnt": n, "occ": n, "m1": (x - shift).abs().sum().item() / D,
+                 "m2": ((x - shift) ** 2).sum().item() / D}
+        rec = {"check": "old_route vs gauss_estep", "B": B, "T": T, "S": S, "D": D}
+        for k in names:
+            rec[k + "_maxdiff_per_scale"] = (ref[k].reshape(-1) - cnt[k]).abs().max().item() / scale[k]
+        rec["loglik_maxrel"] = ((ref["loglik"] - ll).abs() / ll.abs().clamp_min(1.0)).max().item()
+        print(json.dumps(rec))
+        del ref
+    rounds = _pairs(legs)
+    t = {k: sorted(v)[len(v) // 2] for k, v in rounds.items()}
+    byts = B * T * (8 * D + 8 * S)
+    for k in legs:
+        rec = {"kernel": k, "B": B, "T": T, "S": S, "D": D, "us": t[k] * 1e6, "pairs_us": [r * 1e6 for r in rounds[k]]}
+        if k == "gauss_estep":
+            rec.update({"GBps": byts / t[k] / 1e9, "frac_hbm": byts / t[k] / HBM_PEAK})
+        else:
+            rec["x_gauss_estep"] = t[k] / t["gauss_estep"]
+            rec["fused_faster_in_every_pair"] = all(o > f for o, f in zip(rounds[k], rounds["gauss_estep"]))
         print(json.dumps(rec))
 
 
@@ -611,6 +684,7 @@ if __name__ == "__main__":
     ap.add_argument("--T", type=int, default=200)
     ap.add_argument("--K", type=int, default=32)
     ap.add_argument("--V", type=int, default=512)
+    ap.add_argument("--D", type=int, default=16)
     ap.add_argument("--N", type=int, default=64)
     ap.add_argument("--M", type=int, default=8)
     ap.add_argument("--iters", type=int, default=20)
@@ -618,6 +692,6 @@ if __name__ == "__main__":
     a = ap.parse_args()
     {"vq": bench_vq, "stream": bench_stream, "viterbi": bench_viterbi, "fwdbwd": bench_fwdbwd,
      "filter": bench_filter, "xi": bench_xi, "estep": bench_estep, "estep_batched": bench_estep_batched,
-     "code_fit": bench_code_fit, "code_viterbi": bench_code_viterbi,
+     "gauss_estep": bench_gauss_estep, "code_fit": bench_code_fit, "code_viterbi": bench_code_viterbi,
      "code_filter": bench_code_filter, "sample": bench_sample, "vq_stats": bench_vq_stats,
      "vq_bwd": bench_vq_bwd}[a.what](a)

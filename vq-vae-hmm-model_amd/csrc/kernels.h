@@ -535,6 +535,21 @@ int launch_hmm_code_viterbi(const float* log_pi, const float* log_A, const float
 int launch_hmm_code_filter(const float* log_pi, const float* log_A, const float* log_B, const int32_t* codes,
                            const int64_t* lengths, const float* prev, int64_t B, int64_t T, int64_t S, int64_t V,
                            float* filt, float* last, float* loglik, void* ws, hipStream_t s);
+// stationary HMM with diagonal-Gaussian emissions on x (B,T,D), 1 <= S <= 32, 1 <= D <= 64 (hmm_gauss.hip): the
+// emission log-densities, the fused E-step (counts and moments of x - shift in fp64; shift, weights, loglik and
+// gamma nullable; ws = hmm_gauss_estep_ws_bytes) and the ancestral sampler
+bool hmm_gauss_supported(int64_t S, int64_t D);
+size_t hmm_gauss_estep_ws_bytes(int64_t B, int64_t T, int64_t S, int64_t D);
+int launch_hmm_gauss_emission(const float* mean, const float* log_var, const float* x, const int64_t* lengths,
+                              int64_t B, int64_t T, int64_t S, int64_t D, float* em, hipStream_t s);
+int launch_hmm_gauss_estep(const float* log_pi, const float* log_A, const float* mean, const float* log_var,
+                           const float* x, const int64_t* lengths, const float* shift, const float* weights,
+                           int64_t B, int64_t T, int64_t S, int64_t D, double* pi_cnt, double* trans_cnt,
+                           double* occ, double* m1, double* m2, float* loglik, float* gamma, void* ws,
+                           hipStream_t s);
+int launch_hmm_gauss_sample(const float* log_pi, const float* log_A, const float* mean, const float* log_var,
+                            const float* uniforms, const float* normals, int64_t N, int64_t T, int64_t S,
+                            int64_t D, int32_t* states, float* x, hipStream_t s);
 // codebook learning (vq_codebook.hip), 1 <= K <= 65536, 1 <= Dv <= 512, K Dv <= 2^21: per-code count / residual
 // sum / sse in fp64 under given assignments (each nullable here), and with dz the quantizer's backward from the
 // same pass (dz = g_zq + *dz_scale r, dcb = *dcb_scale rsum from the reduce launch); ws = vq_codebook_ws_bytes.

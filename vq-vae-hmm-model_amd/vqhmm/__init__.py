@@ -19,6 +19,7 @@ from .checkpoint import load_checkpoint, load_encoder, save_checkpoint, save_enc
 from .codebook import Codebook  # noqa: E402,F401
 from .codehmm import CodeHMM, code_log_prob  # noqa: E402,F401
 from .codehmm_ensemble import CodeHMMEnsemble  # noqa: E402,F401
+from .gauss_hmm import GaussianHMM, gauss_log_prob  # noqa: E402,F401
 from .data import DeviceChunkLoader, RandomChunkDataset, collate_fn  # noqa: E402,F401
 from .hmm import (forward_backward, forward_filter, pairwise_posteriors, quantize, regime_argmax,  # noqa: E402,F401
                   sample_posterior_paths, simulate_paths, viterbi, vq_argmin)
@@ -30,5 +31,5 @@ from .train import Trainer, TrainState, train_model  # noqa: E402,F401
 __all__ = ["VAE_HMM", "Encoder", "Prior", "Decoder", "train_model", "Trainer", "TrainState", "RandomChunkDataset",
            "collate_fn", "DeviceChunkLoader", "vq_argmin", "quantize", "regime_argmax", "viterbi", "forward_backward", "PARAM_ORDER",
            "save_checkpoint", "load_checkpoint", "save_encoder", "load_encoder", "infer", "hard_regimes", "viterbi_regimes",
-           "prior_viterbi", "forward_filter", "pairwise_posteriors", "filtered_regimes", "CodeHMM", "CodeHMMEnsemble", "code_log_prob", "Codebook",
+           "prior_viterbi", "forward_filter", "pairwise_posteriors", "filtered_regimes", "CodeHMM", "CodeHMMEnsemble", "code_log_prob", "Codebook", "GaussianHMM", "gauss_log_prob",
            "sample_posterior_paths", "simulate_paths", "sampled_regimes", "simulate_regimes"]
