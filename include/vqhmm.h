@@ -73,7 +73,12 @@ int vqhmm_param_layout(const vqhmm_dims_t* dims, int64_t offsets[VQHMM_NPARAMS +
  * s_k = fmaf chain over d ascending of z_d * (-2 c_kd) starting from
  * ||c_k||^2 (itself the fmaf chain of c_kd^2); idx = first k with the
  * smallest s_k; dmin = s_idx + ((q0 + q1) + (q2 + q3)), q_r the fmaf chain of
- * z_d^2 over d = r (mod 4).  Bit-exact vs oracle/c/hmm_oracle.c. */
+ * z_d^2 over d = r (mod 4).  Bit-exact vs oracle/c/hmm_oracle.c, non-finite z
+ * included (a NaN score is never the minimum; where the oracle's dmin is NaN so
+ * is this one).  The inputs z and codebook (of this entry and of
+ * vqhmm_vq_quantize_f32) need only 4-byte alignment and give the same idx, dmin
+ * and z_q_st bits as 16-byte aligned ones (sse then within 1e-6 relative: another
+ * partial-sum order); the outputs and the workspace must be 16-byte aligned. */
 int vqhmm_vq_argmin_f32(const float* z, int64_t B, int64_t Dv, int64_t T,
                         const float* codebook, int64_t K,
                         int32_t* idx, float* dmin, void* stream);
@@ -104,6 +109,9 @@ int vqhmm_vq_quantize_f32(const float* z, int64_t B, int64_t Dv, int64_t T, cons
  * groups, hmm.hip; 8 < K <= 32: one sequence per wave, hmm_wide.hip; 32 < K <= 4096: one workgroup
  * per sequence, states j, j + 256, .. per thread, 16-bit backpointers past 256 states,
  * hmm_generic.hip); larger K -> VQHMM_EUNSUPPORTED.
+ * log_pi, log_A and em need only 4-byte alignment and give the same path and score bits as
+ * 16-byte aligned ones (-inf entries included); path, score and the workspace must be 16-byte
+ * aligned.
  * Workspace: vqhmm_viterbi_workspace_size(B, T, K) bytes (backpointers as one
  * 64-bit lane ballot per step per wave of 64 / KP^2 sequences, KP = K rounded
  * up to a power of two; T rounded up to 64). */
@@ -122,7 +130,11 @@ int vqhmm_viterbi_f32(const float* log_pi, const float* log_A, const float* em, 
  * pass, then per-segment chains; hmm_seg.hip); a sequence that leaves the
  * linear range there is recomputed exactly in the same launch.
  * Workspace: vqhmm_fwdbwd_workspace_size(B, T, K) = 2 * B * T * K * 4 bytes.
- * Accuracy target vs the fp64 oracle: |gamma| abs 1e-5, logZ rel 1e-5.  K <= 4096 (as Viterbi). */
+ * Accuracy target vs the fp64 oracle: |gamma| abs 1e-5, logZ rel 1e-5.  K <= 4096 (as Viterbi).
+ * log_pi, log_A and em need only 4-byte alignment: every kernel variant then meets the same
+ * accuracy target (K = 4 and K = 8 stage the tables in 16-step instead of 32-step chunks, so the
+ * bits may differ from an aligned call's within it); gamma, logZ and the workspace must be 16-byte
+ * aligned (the parallel-in-time kernel stores K = 8 gamma rows as 16-byte vectors). */
 size_t vqhmm_fwdbwd_workspace_size(int64_t B, int64_t T, int64_t K);
 int vqhmm_fwdbwd_f32(const float* log_pi, const float* log_A, const float* em, const int64_t* lengths,
                      int64_t B, int64_t T, int64_t K, float* gamma, float* logZ, void* workspace,
@@ -182,7 +194,8 @@ int vqhmm_fwdbwd_xi_f32(const float* log_pi, const float* log_A, const float* em
  * The paths depend only on the inputs and u, never on the grid, the lane mapping or the kernel
  * variant; two calls give the same bits.  Every global access stays inside its own array (an
  * exact-size allocation is safe), offsets are 64-bit (B*N*T may pass 2^31).  NaN inputs may yield
- * any values in {-1, 0 .. K-1}.
+ * any values in {-1, 0 .. K-1}.  filt / log_pi, log_A and u need only 4-byte alignment and give
+ * the same paths as 16-byte aligned ones; paths must be 16-byte aligned.
  * Return codes, checked in this order on the host before any launch: a negative size ->
  * VQHMM_EINVAL; K outside [1, 32] -> VQHMM_EUNSUPPORTED; B*N*T == 0 -> VQHMM_OK without a launch;
  * a null pointer -> VQHMM_EINVAL.  (T > 2^28 or B >= 2^31: VQHMM_EUNSUPPORTED.) */

@@ -30,7 +30,10 @@ namespace vqhmm {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-template <int S>  // MFMA steps of 2 dims each, 2*S >= Dv
+// S MFMA steps of 2 dims each.  launch_vq_argmin picks the smallest S in {2, 4, 8, 16, 32} with 2 S >= Dv, so
+// for S >= 4 also Dv > S: the slots s < S / 2 (dims 2s, 2s + 1 <= S - 1) are real dims for every Dv, and only
+// the upper half can be padding (a = 0).
+template <int S>
 __global__ __launch_bounds__(256) void vq_mfma_kernel(const float* __restrict__ z, int64_t B, int Dv, int T,
                                                       const float* __restrict__ cb, int K, int32_t* __restrict__ idx,
                                                       float* __restrict__ dmin, int64_t tiles) {
@@ -38,6 +41,7 @@ __global__ __launch_bounds__(256) void vq_mfma_kernel(const float* __restrict__ 
   const int64_t N = B * (int64_t)T;
   const int64_t wave0 = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int64_t nwaves = (int64_t)gridDim.x * 4;
+  constexpr int SR = S >= 4 ? S / 2 : 0;  // slots below SR hold real dims whatever Dv is
 
   auto load = [&](int64_t tile, float* zr) {
     int64_t p = tile * 32 + j;
@@ -45,7 +49,8 @@ __global__ __launch_bounds__(256) void vq_mfma_kernel(const float* __restrict__ 
     const int64_t b = p / T;
     const float* base = z + b * (int64_t)Dv * T + (p - b * T);
 #pragma unroll
-    for (int s = 0; s < S; ++s) zr[s] = base[(int64_t)min(2 * s + h, Dv - 1) * T];  // padded dims: a = 0
+    for (int s = 0; s < S; ++s)  // a padded slot reads dim Dv - 1 (a valid address); its value is dropped below
+      zr[s] = base[(int64_t)(s < SR ? 2 * s + h : min(2 * s + h, Dv - 1)) * T];
   };
   float zc[S];
   if (wave0 < tiles) load(wave0, zc);  // first tile in flight during the codebook prologue
@@ -77,6 +82,10 @@ __global__ __launch_bounds__(256) void vq_mfma_kernel(const float* __restrict__ 
     float zn[S];
     const bool more = tile + nwaves < tiles;
     if (more) load(tile + nwaves, zn);
+    // a padded dim slot holds a real element of z behind a = 0: zeroed, so that 0 * (inf or NaN)
+    // never enters a score (the contract's chain runs over the real dims only)
+#pragma unroll
+    for (int s = SR; s < S; ++s) zc[s] = (2 * s + h < Dv) ? zc[s] : 0.0f;
     f32x16 acc;
 #pragma unroll
     for (int v = 0; v < 16; ++v) acc[v] = init[v];
@@ -86,12 +95,9 @@ __global__ __launch_bounds__(256) void vq_mfma_kernel(const float* __restrict__ 
     // 2+h (s odd); zn = (q0 + q1) + (q2 + q3)
     float qa = 0.0f, qb = 0.0f;  // d mod 4 = h, 2 + h
 #pragma unroll
-    for (int s = 0; s < S; ++s) {
-      const float zv = (2 * s + h < Dv) ? zc[s] : 0.0f;
-      if (2 * s < Dv) {
-        if (s & 1) qb = __builtin_fmaf(zv, zv, qb);
-        else qa = __builtin_fmaf(zv, zv, qa);
-      }
+    for (int s = 0; s < S; ++s) {  // (a padded slot is +0 by now: fmaf(0, 0, q) = q)
+      if (s & 1) qb = __builtin_fmaf(zc[s], zc[s], qb);
+      else qa = __builtin_fmaf(zc[s], zc[s], qa);
     }
     const float pqa = __shfl_xor(qa, 32), pqb = __shfl_xor(qb, 32);
     const float zp = (qa + pqa) + (qb + pqb);
