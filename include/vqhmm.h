@@ -399,6 +399,66 @@ int vqhmm_gauss_sample_f32(const float* log_pi, const float* log_A,
                            int64_t N, int64_t T, int64_t S, int64_t D,
                            int32_t* states, float* x, void* stream);
 
+/* ------------------------- Gaussian HMM with full covariances (hmm_gauss_full.hip) ----
+ * The model of the block above with a full covariance per state: log_pi (S), log_A (S,S), mean (S,D)
+ * as there, and prec_chol (S,D,D) fp32 row-major, W_s = L_s^-1 with Sigma_s = L_s L_s^T: lower-
+ * triangular with a positive diagonal.  The strict upper triangle is never read.  1 <= S <= 32,
+ * 1 <= D <= 32 and S*D*D <= 8192 (else VQHMM_EUNSUPPORTED, and the workspace queries return 0).  x,
+ * lengths, shift and weights are the diagonal block's.
+ *
+ * vqhmm_gauss_full_emission_f32: em (B,T,S) fp32,
+ *   em[b,t,s] = -1/2 |W_s (x - mean_s)|^2 + sum_i log W_s[i,i] - (D/2) ln 2 pi
+ * computed as fma(-1/2, q, c_s): with z_j = x_j - mean_sj, r_i = the fp32 fma chain over j = 0..i in
+ * index order of fma(W_s[i,j], z_j, r_i), q = the fma chain over i in index order of fma(r_i, r_i, q);
+ * c_s = sum_i log W_s[i,i] - (D/2) ln 2 pi summed in fp64 and rounded once (a non-positive diagonal
+ * makes c_s, and the state's emissions, NaN).  Rows at t >= length are -inf; every element is written.
+ * Accuracy target vs fp64 on the same fp32 inputs: (3 D + 16) 2^-23 A with A = 1/2 sum_i (sum_{j<=i}
+ * |W_ij| |z_j|)^2 + |sum_i log W_ii| + (D/2) ln 2 pi.  No workspace.
+ *
+ * vqhmm_gauss_full_estep_f32: vqhmm_gauss_estep_f32 with these emissions.  pi_cnt, trans_cnt, occ and
+ * m1 are that entry's; the second moments are full,
+ *   m2 (S,D,D) = sum_b w_b sum_{t < L_b} gamma_{b,t}(s) (x_{b,t,i} - shift_i) (x_{b,t,j} - shift_j):
+ * the triangle j <= i is computed and written to [s,i,j] and [s,j,i], so m2 is symmetric bit for bit.
+ * Every element of the five counts is written.  Everything else the diagonal entry states holds here
+ * word for word: shift, weights (all ones = the bits of NULL), nullable loglik and gamma that do not
+ * depend on the weights or on the rest of the batch, emissions that are bit for bit what
+ * vqhmm_gauss_full_emission_f32 writes and never reach memory, the chain and its rare path, length 0 /
+ * impossible / non-finite sequences (loglik NaN / -inf / NaN, zero contribution, zero gamma rows),
+ * determinism, graph capture, 64-bit offsets, in-bounds access of exact-size and 4-byte-misaligned
+ * buffers, and the accuracy targets, with m2[s,i,j] within 2e-5 of sum |x_i - shift_i| |x_j - shift_j|.
+ * Workspace: vqhmm_gauss_full_estep_workspace_size(B, T, S, D) bytes.
+ *
+ * vqhmm_gauss_moments_f32: occ (S), m1 (S,D) and m2 (S,D,D) as above, under a caller-supplied gamma
+ * (B,T,S) fp32 (an encoder's posterior, a filter's output) in place of the chain's: the per-regime
+ * weighted sums behind a pooled regime mean and covariance.  gamma at t >= length is never read.  A
+ * sequence with a non-finite x or gamma inside its length contributes exactly 0.  Three launches (the
+ * flags of such sequences, one wave per sequence and 64-step chunk, the E-step's fixed-order
+ * reduction); deterministic, no atomics, graph-capturable, same addressing guarantees.  Workspace:
+ * vqhmm_gauss_moments_workspace_size(B, T, S, D) bytes.
+ *
+ * Return codes: the diagonal block's, in its order.  B*T == 0 -> VQHMM_OK without a launch, the counts
+ * (E-step: five, moments: three; they must not be NULL: VQHMM_EINVAL) zeroed and loglik = NaN for
+ * B > 0. */
+int vqhmm_gauss_full_emission_f32(const float* mean, const float* prec_chol,
+                                  const float* x, const int64_t* lengths,
+                                  int64_t B, int64_t T, int64_t S, int64_t D,
+                                  float* em, void* stream);
+size_t vqhmm_gauss_full_estep_workspace_size(int64_t B, int64_t T, int64_t S, int64_t D);
+int vqhmm_gauss_full_estep_f32(const float* log_pi, const float* log_A,
+                               const float* mean, const float* prec_chol,
+                               const float* x, const int64_t* lengths,
+                               const float* shift, const float* weights,
+                               int64_t B, int64_t T, int64_t S, int64_t D,
+                               double* pi_cnt, double* trans_cnt, double* occ, double* m1, double* m2,
+                               float* loglik, float* gamma,
+                               void* workspace, size_t ws_bytes, void* stream);
+size_t vqhmm_gauss_moments_workspace_size(int64_t B, int64_t T, int64_t S, int64_t D);
+int vqhmm_gauss_moments_f32(const float* x, const float* gamma, const int64_t* lengths,
+                            const float* shift, const float* weights,
+                            int64_t B, int64_t T, int64_t S, int64_t D,
+                            double* occ, double* m1, double* m2,
+                            void* workspace, size_t ws_bytes, void* stream);
+
 /* -------------------------------------------------- codebook learning ----
  * Per-code statistics of a batch under given assignments, the quantizer's backward from the same
  * pass, and the channels-first lookup (pseudocode.txt:8-32, the codebook's side; vq_codebook.hip).

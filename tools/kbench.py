@@ -14,6 +14,12 @@
                                                         (the fused Gaussian-HMM E-step on x (B,T,D); --old-route: also
                                                          torch emissions + expanded log_A + pairwise_posteriors + torch
                                                          moment sums, in five alternating pairs, and a check line)
+    python tools/kbench.py gauss_full_estep --B 2048 --T 200 --K 32 --D 16 [--old-route]
+    python tools/kbench.py gauss_moments --B 2048 --T 200 --K 32 --D 16 [--old-route]
+                                                        (the full-covariance E-step / the regime moments under a given
+                                                         gamma; --old-route: also the torch route (triangular solve,
+                                                         emissions, expanded log_A, pairwise_posteriors, fp64 einsum /
+                                                         the fp64 einsum alone), five alternating pairs, a check line)
     python tools/kbench.py code_fit --B 256 --T 200 --K 8 --V 512 --M 8 [--iters 20]
                                                         (--iters EM iterations of CodeHMMEnsemble.fit against --M
                                                          sequential CodeHMM.fit(n_init=1) runs, five alternating pairs)
@@ -388,6 +394,132 @@ def bench_gauss_estep(a):
         print(json.dumps(rec))
 
 
+def _full_case(B, T, S, D):
+    """A full-covariance model with random correlated covariances, data around its means, full lengths."""
+    g = torch.Generator(device="cuda").manual_seed(11)
+    hmm = vqhmm.GaussianHMM(S, D, covariance_type="full", generator=torch.Generator().manual_seed(3)).cuda()
+    with torch.no_grad():
+        hmm.mean.mul_(2.0)
+        Lc = torch.randn((S, D, D), device="cuda", generator=g).tril(-1) * (0.4 / math.sqrt(D))
+        hmm.scale_tril.copy_(Lc + torch.diag_embed(torch.rand((S, D), device="cuda", generator=g) + 0.6))
+    z = torch.randint(0, S, (B, T), device="cuda", generator=g)
+    x = hmm.mean[z] + torch.randn((B, T, D), device="cuda", generator=g)
+    L = torch.full((B,), T, dtype=torch.int64, device="cuda")
+    return hmm, x.contiguous(), L, x.mean((0, 1)).contiguous()
+
+
+def _report(legs, rounds, new, dims, extra=None):
+    t = {k: sorted(v)[len(v) // 2] for k, v in rounds.items()}
+    for k in legs:
+        rec = dict({"kernel": k}, **dims, us=t[k] * 1e6, pairs_us=[r * 1e6 for r in rounds[k]])
+        if k == new:
+            rec.update(extra(t[k]) if extra else {})
+        else:
+            rec["x_" + new] = t[k] / t[new]
+            rec["fused_faster_in_every_pair"] = all(o > f for o, f in zip(rounds[k], rounds[new]))
+        print(json.dumps(rec))
+
+
+def bench_gauss_full_estep(a):
+    """vqhmm_gauss_full_estep_f32 (counts + loglik, no gamma) at S = --K states on x (B,T,--D).  --old-route: also
+    the torch way to the same statistics (W by solve_triangular, the emissions by a batched product into (B,T,S),
+    log_A expanded to (B,T,S,S), pairwise_posteriors, the moments by fp64 einsum; all inside the timed call), in
+    five alternating pairs after a warm-up, and a check line with the largest differences between the two routes'
+    counts relative to the tests' bounds' scales."""
+    B, T, S, D = a.B, a.T, a.K, a.D
+    hmm, x, L, shift = _full_case(B, T, S, D)
+    lib = vqhmm._ext.load()
+    P = vqhmm._ext.ptr
+    st = vqhmm._ext.stream_ptr()
+    names = ("pi_cnt", "trans_cnt", "occ", "m1", "m2")
+    cnt = {k: torch.empty(n, dtype=torch.float64, device="cuda")
+           for k, n in zip(names, (S, S * S, S, S * D, S * D * D))}
+    ll = torch.empty(B, device="cuda")
+    nb = lib.vqhmm_gauss_full_estep_workspace_size(B, T, S, D)
+    ws = torch.empty(max(nb, 1), dtype=torch.uint8, device="cuda")
+    W = hmm.precisions_cholesky
+
+    def new():
+        lib.vqhmm_gauss_full_estep_f32(P(hmm.log_pi), P(hmm.log_A), P(hmm.mean), P(W), P(x), P(L), P(shift), None,
+                                       B, T, S, D, *(P(cnt[k]) for k in names), P(ll), None, P(ws), nb, st)
+
+    def old():
+        eye = torch.eye(D, device="cuda").expand(S, D, D)
+        Wt = torch.linalg.solve_triangular(hmm.scale_tril, eye, upper=False)
+        em = torch.empty((B, T, S), device="cuda")
+        for s in range(S):   # (B T, D) x (D, D) per state: the (B,T,S,D) intermediate never exists
+            r = (x - hmm.mean[s]).reshape(-1, D) @ Wt[s].T
+            em[:, :, s] = (-0.5 * (r * r).sum(-1) + torch.log(torch.diagonal(Wt[s])).sum()
+                           - 0.5 * D * math.log(2 * math.pi)).view(B, T)
+        gamma, xi, logZ = vqhmm.pairwise_posteriors(hmm.log_pi, hmm.log_A.expand(B, T, S, S), em, L)
+        y = (x - shift).double()
+        gd = gamma.double()
+        return {"pi_cnt": gamma[:, 0].sum(0, dtype=torch.float64), "trans_cnt": xi.sum((0, 1), dtype=torch.float64),
+                "occ": gd.sum((0, 1)), "m1": torch.einsum("bts,btd->sd", gd, y),
+                "m2": torch.einsum("bts,bti,btj->sij", gd, y, y), "loglik": logZ}
+
+    legs = {"gauss_full_estep": new}
+    if a.old_route:
+        legs["old_route"] = old
+        ref = old()
+        new()
+        torch.cuda.synchronize()
+        n = B * T
+        ya = (x - shift).abs()
+        scale = {"pi_cnt": B, "trans_cnt": n, "occ": n, "m1": ya.sum().item() / D, "m2": (ya ** 2).sum().item() / D}
+        rec = {"check": "old_route vs gauss_full_estep", "B": B, "T": T, "S": S, "D": D}
+        for k in names:
+            rec[k + "_maxdiff_per_scale"] = (ref[k].reshape(-1) - cnt[k]).abs().max().item() / scale[k]
+        rec["loglik_maxrel"] = ((ref["loglik"] - ll).abs() / ll.abs().clamp_min(1.0)).max().item()
+        print(json.dumps(rec))
+        del ref
+    byts = B * T * (8 * D + 8 * S)
+    _report(legs, _pairs(legs), "gauss_full_estep", {"B": B, "T": T, "S": S, "D": D},
+            lambda t: {"GBps": byts / t / 1e9, "frac_hbm": byts / t / HBM_PEAK})
+
+
+def bench_gauss_moments(a):
+    """vqhmm_gauss_moments_f32 (occ, m1, m2 under a given gamma (B,T,--K)) on x (B,T,--D).  --old-route: also the
+    fp64 einsum of the same sums, in five alternating pairs, and a check line."""
+    B, T, S, D = a.B, a.T, a.K, a.D
+    hmm, x, L, shift = _full_case(B, T, S, D)
+    gamma = torch.softmax(torch.randn((B, T, S), device="cuda", generator=torch.Generator(device="cuda").manual_seed(5)), -1)
+    lib = vqhmm._ext.load()
+    P = vqhmm._ext.ptr
+    st = vqhmm._ext.stream_ptr()
+    names = ("occ", "m1", "m2")
+    cnt = {k: torch.empty(n, dtype=torch.float64, device="cuda") for k, n in zip(names, (S, S * D, S * D * D))}
+    nb = lib.vqhmm_gauss_moments_workspace_size(B, T, S, D)
+    ws = torch.empty(max(nb, 1), dtype=torch.uint8, device="cuda")
+
+    def new():
+        lib.vqhmm_gauss_moments_f32(P(x), P(gamma), P(L), P(shift), None, B, T, S, D, *(P(cnt[k]) for k in names),
+                                    P(ws), nb, st)
+
+    def old():
+        y = (x - shift).double()
+        gd = gamma.double()
+        return {"occ": gd.sum((0, 1)), "m1": torch.einsum("bts,btd->sd", gd, y),
+                "m2": torch.einsum("bts,bti,btj->sij", gd, y, y)}
+
+    legs = {"gauss_moments": new}
+    if a.old_route:
+        legs["old_route"] = old
+        ref = old()
+        new()
+        torch.cuda.synchronize()
+        ya = (x - shift).abs()
+        scale = {"occ": B * T, "m1": ya.sum().item() / D, "m2": (ya ** 2).sum().item() / D}
+        rec = {"check": "old_route vs gauss_moments", "B": B, "T": T, "S": S, "D": D}
+        for k in names:
+            rec[k + "_maxdiff_per_scale"] = (ref[k].reshape(-1) - cnt[k]).abs().max().item() / scale[k]
+        print(json.dumps(rec))
+        del ref
+    byts = B * T * (8 * D + 8 * S)   # x and gamma, each read by the flag launch and by the product
+    _report(legs, _pairs(legs), "gauss_moments", {"B": B, "T": T, "S": S, "D": D},
+            lambda t: {"GBps": byts / t / 1e9, "frac_hbm": byts / t / HBM_PEAK})
+
+
 def bench_code_fit(a):
     """--iters EM iterations of CodeHMMEnsemble.fit on --M members against --M sequential CodeHMM.fit(n_init=1)
     runs from the same starts (every timed call starts from a copy of them), five alternating pairs."""
@@ -692,6 +824,7 @@ if __name__ == "__main__":
     a = ap.parse_args()
     {"vq": bench_vq, "stream": bench_stream, "viterbi": bench_viterbi, "fwdbwd": bench_fwdbwd,
      "filter": bench_filter, "xi": bench_xi, "estep": bench_estep, "estep_batched": bench_estep_batched,
-     "gauss_estep": bench_gauss_estep, "code_fit": bench_code_fit, "code_viterbi": bench_code_viterbi,
+     "gauss_estep": bench_gauss_estep, "gauss_full_estep": bench_gauss_full_estep,
+     "gauss_moments": bench_gauss_moments, "code_fit": bench_code_fit, "code_viterbi": bench_code_viterbi,
      "code_filter": bench_code_filter, "sample": bench_sample, "vq_stats": bench_vq_stats,
      "vq_bwd": bench_vq_bwd}[a.what](a)

@@ -501,6 +501,50 @@ int vqhmm_gauss_sample_f32(const float* log_pi, const float* log_A, const float*
                                  (hipStream_t)stream);
 }
 
+int vqhmm_gauss_full_emission_f32(const float* mean, const float* prec_chol, const float* x, const int64_t* lengths,
+                                  int64_t B, int64_t T, int64_t S, int64_t D, float* em, void* stream) {
+  if (B < 0 || T < 0 || S < 0 || D < 0) return VQHMM_EINVAL;
+  if (!hmm_gauss_full_supported(S, D)) return VQHMM_EUNSUPPORTED;
+  if (B * T == 0) return VQHMM_OK;
+  if (!mean || !prec_chol || !x || !lengths || !em) return VQHMM_EINVAL;
+  return launch_hmm_gauss_full_emission(mean, prec_chol, x, lengths, B, T, S, D, em, (hipStream_t)stream);
+}
+
+size_t vqhmm_gauss_full_estep_workspace_size(int64_t B, int64_t T, int64_t S, int64_t D) {
+  return hmm_gauss_full_estep_ws_bytes(B, T, S, D);
+}
+
+int vqhmm_gauss_full_estep_f32(const float* log_pi, const float* log_A, const float* mean, const float* prec_chol,
+                               const float* x, const int64_t* lengths, const float* shift, const float* weights,
+                               int64_t B, int64_t T, int64_t S, int64_t D, double* pi_cnt, double* trans_cnt,
+                               double* occ, double* m1, double* m2, float* loglik, float* gamma, void* ws,
+                               size_t ws_bytes, void* stream) {
+  if (B < 0 || T < 0 || S < 0 || D < 0) return VQHMM_EINVAL;
+  if (!hmm_gauss_full_supported(S, D)) return VQHMM_EUNSUPPORTED;
+  if (!pi_cnt || !trans_cnt || !occ || !m1 || !m2) return VQHMM_EINVAL;  // written whatever B and T are
+  if (B * T > 0 && (!log_pi || !log_A || !mean || !prec_chol || !x || !lengths || !ws ||
+                    ws_bytes < hmm_gauss_full_estep_ws_bytes(B, T, S, D)))
+    return VQHMM_EINVAL;
+  return launch_hmm_gauss_full_estep(log_pi, log_A, mean, prec_chol, x, lengths, shift, weights, B, T, S, D, pi_cnt,
+                                     trans_cnt, occ, m1, m2, loglik, gamma, ws, (hipStream_t)stream);
+}
+
+size_t vqhmm_gauss_moments_workspace_size(int64_t B, int64_t T, int64_t S, int64_t D) {
+  return hmm_gauss_moments_ws_bytes(B, T, S, D);
+}
+
+int vqhmm_gauss_moments_f32(const float* x, const float* gamma, const int64_t* lengths, const float* shift,
+                            const float* weights, int64_t B, int64_t T, int64_t S, int64_t D, double* occ,
+                            double* m1, double* m2, void* ws, size_t ws_bytes, void* stream) {
+  if (B < 0 || T < 0 || S < 0 || D < 0) return VQHMM_EINVAL;
+  if (!hmm_gauss_full_supported(S, D)) return VQHMM_EUNSUPPORTED;
+  if (!occ || !m1 || !m2) return VQHMM_EINVAL;  // written whatever B and T are
+  if (B * T > 0 && (!x || !gamma || !lengths || !ws || ws_bytes < hmm_gauss_moments_ws_bytes(B, T, S, D)))
+    return VQHMM_EINVAL;
+  return launch_hmm_gauss_moments(x, gamma, lengths, shift, weights, B, T, S, D, occ, m1, m2, ws,
+                                  (hipStream_t)stream);
+}
+
 size_t vqhmm_vq_stats_workspace_size(int64_t B, int64_t Dv, int64_t T, int64_t K) {
   return vq_codebook_ws_bytes(B, Dv, T, K);
 }

@@ -550,6 +550,22 @@ int launch_hmm_gauss_estep(const float* log_pi, const float* log_A, const float*
 int launch_hmm_gauss_sample(const float* log_pi, const float* log_A, const float* mean, const float* log_var,
                             const float* uniforms, const float* normals, int64_t N, int64_t T, int64_t S,
                             int64_t D, int32_t* states, float* x, hipStream_t s);
+// ... with full-covariance emissions, prec_chol (S,D,D) = the lower-triangular inverse Cholesky factors, 1 <= S,
+// D <= 32, S D D <= 8192 (hmm_gauss_full.hip): the emission log-densities, the fused E-step (m2 (S,D,D), both
+// triangles) and the (occ, m1, m2) moments under a given gamma (B,T,S); ws = the matching *_ws_bytes
+bool hmm_gauss_full_supported(int64_t S, int64_t D);
+size_t hmm_gauss_full_estep_ws_bytes(int64_t B, int64_t T, int64_t S, int64_t D);
+size_t hmm_gauss_moments_ws_bytes(int64_t B, int64_t T, int64_t S, int64_t D);
+int launch_hmm_gauss_full_emission(const float* mean, const float* prec_chol, const float* x, const int64_t* lengths,
+                                   int64_t B, int64_t T, int64_t S, int64_t D, float* em, hipStream_t s);
+int launch_hmm_gauss_full_estep(const float* log_pi, const float* log_A, const float* mean, const float* prec_chol,
+                                const float* x, const int64_t* lengths, const float* shift, const float* weights,
+                                int64_t B, int64_t T, int64_t S, int64_t D, double* pi_cnt, double* trans_cnt,
+                                double* occ, double* m1, double* m2, float* loglik, float* gamma, void* ws,
+                                hipStream_t s);
+int launch_hmm_gauss_moments(const float* x, const float* gamma, const int64_t* lengths, const float* shift,
+                             const float* weights, int64_t B, int64_t T, int64_t S, int64_t D, double* occ,
+                             double* m1, double* m2, void* ws, hipStream_t s);
 // codebook learning (vq_codebook.hip), 1 <= K <= 65536, 1 <= Dv <= 512, K Dv <= 2^21: per-code count / residual
 // sum / sse in fp64 under given assignments (each nullable here), and with dz the quantizer's backward from the
 // same pass (dz = g_zq + *dz_scale r, dcb = *dcb_scale rsum from the reduce launch); ws = vq_codebook_ws_bytes.

@@ -71,6 +71,15 @@ _SIGS = {
                                              c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "vqhmm_gauss_sample_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp,
                                               c_vp, c_vp]),
+    "vqhmm_gauss_full_emission_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp,
+                                                     c_vp]),
+    "vqhmm_gauss_full_estep_workspace_size": (c_sz, [c_i64, c_i64, c_i64, c_i64]),
+    "vqhmm_gauss_full_estep_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64,
+                                                  c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz,
+                                                  c_vp]),
+    "vqhmm_gauss_moments_workspace_size": (c_sz, [c_i64, c_i64, c_i64, c_i64]),
+    "vqhmm_gauss_moments_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp,
+                                               c_vp, c_vp, c_sz, c_vp]),
     "vqhmm_vq_stats_workspace_size": (c_sz, [c_i64, c_i64, c_i64, c_i64]),
     "vqhmm_vq_stats_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp,
                                           c_sz, c_vp]),

@@ -5,6 +5,12 @@ vqhmm_gauss_estep_f32 / vqhmm_gauss_sample_f32, contracts in include/vqhmm.h); t
 of torch arithmetic in fp64 on the device.  With every row of A tied to pi (`as_mixture`, `fit(mixture=True)`)
 the model is a diagonal Gaussian mixture.  `gauss_log_prob` is the differentiable log-likelihood (its backward
 is one weighted E-step).
+
+covariance_type="full" gives every state a full covariance Sigma_s = L_s L_s^T (parameter scale_tril = L_s): the
+kernels of hmm_gauss_full.hip (vqhmm_gauss_full_emission_f32 / vqhmm_gauss_full_estep_f32) take W_s = L_s^-1 and
+return the S x D x D second moments; the M-step adds sklearn's reg_covar to the diagonal and factors in fp64 on the
+device.  `gauss_full_log_prob` is its differentiable log-likelihood, `regime_moments` / `regime_covariance` the
+same moments under a caller-supplied posterior (vqhmm_gauss_moments_f32).
 """
 import torch
 
@@ -14,6 +20,18 @@ from .codehmm import CodeHMM
 
 MAX_STATES = 32   # the kernels' limits (hmm_gauss.hip)
 MAX_DIM = 64
+MAX_DIM_FULL = 32      # hmm_gauss_full.hip: 1 <= D <= 32 and S * D * D <= MAX_SDD_FULL
+MAX_SDD_FULL = 8192
+
+
+def _full_supported(S, D):
+    return 1 <= S <= MAX_STATES and 1 <= D <= MAX_DIM_FULL and S * D * D <= MAX_SDD_FULL
+
+
+def _full_domain(what, S, D):
+    if not _full_supported(S, D):
+        raise ValueError(f"{what}: full covariances need 1 <= S <= {MAX_STATES}, 1 <= D <= {MAX_DIM_FULL} and "
+                         f"S * D * D <= {MAX_SDD_FULL} (got {S}, {D})")
 
 
 def _check_x(what, ref, x, lengths, D):
@@ -107,19 +125,196 @@ def gauss_log_prob(log_pi, log_A, mean, log_var, x, lengths=None):
                                lengths)
 
 
+# ------------------------------------------------------------------ full covariances
+def _prec_chol(scale_tril):
+    """W = L^-1 (S,D,D) fp32 from the lower Cholesky factors L of the covariances: derived in fp64 on the device,
+    rounded once, the strict upper triangle exactly 0."""
+    L = scale_tril.detach().double().tril()
+    eye = torch.eye(L.shape[-1], dtype=torch.float64, device=L.device).expand_as(L)
+    return torch.linalg.solve_triangular(L, eye, upper=False).tril().float().contiguous()
+
+
+def _cholesky(cov):
+    """Lower Cholesky factors of cov (S,D,D) fp64 and a per-matrix success mask, without a host sync:
+    torch.linalg.cholesky_ex, or (a build without it on the device) the D-step column algorithm in torch ops."""
+    try:
+        L, info = torch.linalg.cholesky_ex(cov)
+        return L, (info == 0) & torch.isfinite(L).all((-1, -2))
+    except RuntimeError:
+        D = cov.shape[-1]
+        L = torch.zeros_like(cov)
+        ok = torch.ones(cov.shape[:-2], dtype=torch.bool, device=cov.device)
+        for k in range(D):
+            d = cov[..., k, k] - (L[..., k, :k] ** 2).sum(-1)
+            ok = ok & (d > 0)
+            r = torch.sqrt(torch.where(d > 0, d, torch.ones_like(d)))
+            L[..., k, k] = r
+            if k + 1 < D:
+                c = cov[..., k + 1:, k] - (L[..., k + 1:, :k] * L[..., k:k + 1, :k]).sum(-1)
+                L[..., k + 1:, k] = c / r.unsqueeze(-1)
+        return L, ok & torch.isfinite(L).all((-1, -2))
+
+
+def _estep_full(what, log_pi, log_A, mean, prec, x, lengths, shift, weights, want_loglik, want_gamma):
+    """vqhmm_gauss_full_estep_f32 on contiguous fp32 device tensors -> dict of the fp64 counts (views of `flat`:
+    pi_cnt, trans_cnt, occ, m1, m2 (S,D,D)) [, loglik (B) fp32] [, gamma (B,T,S) fp32] and the shift used."""
+    S, D = mean.shape
+    B, T = x.shape[:2]
+    dev = x.device
+    flat = torch.empty(S + S * S + S + S * D + S * D * D, dtype=torch.float64, device=dev)
+    o = [0, S, S + S * S, 2 * S + S * S, 2 * S + S * S + S * D]
+    out = {"pi_cnt": flat[o[0]:o[1]], "trans_cnt": flat[o[1]:o[2]].view(S, S), "occ": flat[o[2]:o[3]],
+           "m1": flat[o[3]:o[4]].view(S, D), "m2": flat[o[4]:].view(S, D, D), "flat": flat, "shift": shift}
+    loglik = torch.empty((B,), dtype=torch.float32, device=dev) if want_loglik else None
+    gamma = torch.empty((B, T, S), dtype=torch.float32, device=dev) if want_gamma else None
+    lib = _ext.load()
+    nb = lib.vqhmm_gauss_full_estep_workspace_size(B, T, S, D)
+    ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=dev)
+    with torch.no_grad():
+        _ext.check(lib.vqhmm_gauss_full_estep_f32(
+            _ext.ptr(log_pi), _ext.ptr(log_A), _ext.ptr(mean), _ext.ptr(prec), _ext.ptr(x), _ext.ptr(lengths),
+            _ext.ptr(shift), _ext.ptr(weights), B, T, S, D, _ext.ptr(out["pi_cnt"]), _ext.ptr(out["trans_cnt"]),
+            _ext.ptr(out["occ"]), _ext.ptr(out["m1"]), _ext.ptr(out["m2"]), _ext.ptr(loglik), _ext.ptr(gamma),
+            _ext.ptr(ws), nb, _ext.stream_ptr(dev)), what)
+    if want_loglik:
+        out["loglik"] = loglik
+    if want_gamma:
+        out["gamma"] = gamma
+    return out
+
+
+class _GaussFullLogProb(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, log_pi, log_A, mean, scale_tril, x, lengths):
+        prec = _prec_chol(scale_tril)
+        ll = _estep_full("gauss_full_log_prob", log_pi, log_A, mean, prec, x, lengths, None, None, True,
+                         False)["loglik"]
+        ctx.save_for_backward(log_pi, log_A, mean, scale_tril, prec, x, lengths)
+        return ll
+
+    @staticmethod
+    def backward(ctx, g):
+        log_pi, log_A, mean, scale_tril, prec, x, lengths = ctx.saved_tensors
+        w = g.detach().to(torch.float32).reshape(-1).contiguous()
+        shift = mean.mean(0).contiguous()   # moments about the centre of the means, as gauss_log_prob
+        c = _estep_full("gauss_full_log_prob backward", log_pi, log_A, mean, prec, x, lengths, shift, w, False,
+                        False)
+        occ = c["occ"]
+        dm = mean.double() - shift.double()
+        m1 = c["m1"]
+        r1 = m1 - dm * occ[:, None]                                         # sum w gamma (x - mu)
+        dm1 = dm[:, :, None] * m1[:, None, :]
+        r2 = c["m2"] - dm1 - dm1.transpose(1, 2) + occ[:, None, None] * dm[:, :, None] * dm[:, None, :]
+        L = scale_tril.double().tril()
+        eye = torch.eye(L.shape[-1], dtype=torch.float64, device=L.device).expand_as(L)
+        W = torch.linalg.solve_triangular(L, eye, upper=False)
+        sinv = W.transpose(1, 2) @ W
+        g_sigma = 0.5 * sinv @ (r2 - occ[:, None, None] * (L @ L.transpose(1, 2))) @ sinv
+        return (c["pi_cnt"].float(), c["trans_cnt"].float(), (sinv @ r1.unsqueeze(-1)).squeeze(-1).float(),
+                (2.0 * g_sigma @ L).tril().float(), None, None)
+
+
+def gauss_full_log_prob(log_pi, log_A, mean, scale_tril, x, lengths=None):
+    """log p(x[b, :lengths[b]]) (B,) fp32 under the full-covariance Gaussian HMM (log_pi (S,), log_A (S,S), mean
+    (S,D), scale_tril (S,D,D) = the lower Cholesky factors L_s of the covariances; fp32 device tensors),
+    differentiable with respect to the four parameter tensors.  The forward is the fused full E-step's loglik;
+    the backward is one weighted full E-step about shift = mean.mean(0): with R2_s = sum w gamma (x - mu_s)(x -
+    mu_s)^T rebuilt from (occ, m1, m2), d/dmean = Sigma^-1 (m1 - (mu - shift) occ), G = 1/2 Sigma^-1 (R2 - occ
+    Sigma) Sigma^-1 and d/dscale_tril = tril(2 G L).  Only the lower triangle of scale_tril is read.  A sequence
+    whose loglik is not finite contributes exactly zero gradient.  x is data: it raises if x.requires_grad."""
+    if not torch.is_tensor(mean) or mean.dim() != 2:
+        raise ValueError("gauss_full_log_prob: mean must be a float32 tensor of shape (S, D)")
+    S, D = int(mean.shape[0]), int(mean.shape[1])
+    for name, t, shape in (("log_pi", log_pi, (S,)), ("log_A", log_A, (S, S)), ("mean", mean, (S, D)),
+                           ("scale_tril", scale_tril, (S, D, D))):
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or tuple(t.shape) != shape:
+            raise ValueError(f"gauss_full_log_prob: {name} must be a float32 tensor of shape {shape}")
+    _full_domain("gauss_full_log_prob", S, D)
+    if torch.is_tensor(x) and x.requires_grad:
+        raise ValueError("gauss_full_log_prob: x is data and gets no gradient (x.requires_grad is set)")
+    _ext.require_device(log_pi, log_A, mean, scale_tril)
+    x, lengths, _, _ = _check_x("gauss_full_log_prob", log_pi, x, lengths, D)
+    return _GaussFullLogProb.apply(log_pi.contiguous(), log_A.contiguous(), mean.contiguous(),
+                                   scale_tril.contiguous(), x, lengths)
+
+
+def regime_moments(x, gamma, lengths=None, weights=None, shift=None):
+    """The per-regime weighted moments of x (B,T,D) under a given posterior gamma (B,T,S) (an encoder's q, a
+    filter's output; any non-negative weights), pooled over the batch (vqhmm_gauss_moments_f32) -> dict(occ (S,),
+    m1 (S,D), m2 (S,D,D) fp64, flat, shift): occ = sum_b w_b sum_t gamma, m1 = sum w gamma (x - shift), m2 = sum w
+    gamma (x - shift)(x - shift)^T (exactly symmetric).  `flat` is the one buffer they are views of.  A sequence
+    with a non-finite x or gamma inside its length contributes nothing."""
+    if not torch.is_tensor(gamma) or gamma.dim() != 3 or not gamma.dtype.is_floating_point:
+        raise ValueError("regime_moments: gamma must be a floating point tensor of shape (B, T, S)")
+    _ext.require_device(gamma)
+    if not torch.is_tensor(x) or x.dim() != 3:
+        raise ValueError("regime_moments: x must be a tensor of shape (B, T, D)")
+    S, D = int(gamma.shape[2]), int(x.shape[2])
+    _full_domain("regime_moments", S, D)
+    x, lengths, B, T = _check_x("regime_moments", gamma, x, lengths, D)
+    if tuple(gamma.shape[:2]) != (B, T):
+        raise ValueError(f"regime_moments: gamma must have shape ({B}, {T}, S)")
+    gamma = gamma.detach().to(torch.float32).contiguous()
+    dev = x.device
+    if shift is not None:
+        shift = torch.as_tensor(shift).to(dev, torch.float32).contiguous()
+        if shift.shape != (D,):
+            raise ValueError(f"regime_moments: shift must have shape ({D},)")
+    if weights is not None:
+        weights = torch.as_tensor(weights).to(dev, torch.float32).contiguous()
+        if weights.shape != (B,):
+            raise ValueError(f"regime_moments: weights must have shape ({B},)")
+    flat = torch.empty(S + S * D + S * D * D, dtype=torch.float64, device=dev)
+    out = {"occ": flat[:S], "m1": flat[S:S + S * D].view(S, D), "m2": flat[S + S * D:].view(S, D, D), "flat": flat,
+           "shift": shift}
+    lib = _ext.load()
+    nb = lib.vqhmm_gauss_moments_workspace_size(B, T, S, D)
+    ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=dev)
+    with torch.no_grad():
+        _ext.check(lib.vqhmm_gauss_moments_f32(
+            _ext.ptr(x), _ext.ptr(gamma), _ext.ptr(lengths), _ext.ptr(shift), _ext.ptr(weights), B, T, S, D,
+            _ext.ptr(out["occ"]), _ext.ptr(out["m1"]), _ext.ptr(out["m2"]), _ext.ptr(ws), nb,
+            _ext.stream_ptr(dev)), "regime_moments")
+    return out
+
+
+def regime_covariance(x, gamma, lengths=None):
+    """-> (mean (S,D), cov (S,D,D)) fp64: the gamma-weighted mean and (biased) covariance of x per regime, pooled
+    over the batch; the moments are taken about the data mean.  A regime nothing was counted into gets NaN."""
+    if not torch.is_tensor(x) or x.dim() != 3:
+        raise ValueError("regime_covariance: x must be a tensor of shape (B, T, D)")
+    xc, lc, B, T = _check_x("regime_covariance", gamma, x, lengths, int(x.shape[2]))
+    mask = (torch.arange(T, device=xc.device).unsqueeze(0) < lc.clamp(0, T).unsqueeze(1)).unsqueeze(2)
+    shift = (torch.where(mask, xc.double(), 0.0).sum((0, 1)) / mask.sum().clamp_min(1)).float().contiguous()
+    c = regime_moments(xc, gamma, lc, None, shift)
+    occ = c["occ"]
+    o = torch.where(occ > 0, occ, torch.full_like(occ, float("nan")))
+    mu = c["m1"] / o[:, None]
+    cov = c["m2"] / o[:, None, None] - mu[:, :, None] * mu[:, None, :]
+    return mu + shift.double(), cov
+
+
 class GaussianHMM(torch.nn.Module):
-    """HMM with `num_states` hidden states emitting `dim`-dimensional diagonal Gaussians.
+    """HMM with `num_states` hidden states emitting `dim`-dimensional Gaussians, diagonal
+    (covariance_type="diag", the default) or with a full covariance per state ("full").
 
     Parameters (fp32): log_pi (S,), log_A (S,S) with log_A[i,j] = log p(z_t=j | z_{t-1}=i) (natural logs; -inf
-    entries are structural zeros that EM keeps), mean (S,D), log_var (S,D).  They start random (from
-    `generator`): pi and A row-normalised, means standard normal, unit variances."""
+    entries are structural zeros that EM keeps), mean (S,D), and log_var (S,D) ("diag") or scale_tril (S,D,D)
+    ("full": the lower Cholesky factor of each covariance, of which only the lower triangle is read).  They start
+    random (from `generator`): pi and A row-normalised, means standard normal, unit (identity) covariances."""
 
-    def __init__(self, num_states, dim, generator=None):
+    def __init__(self, num_states, dim, covariance_type="diag", generator=None):
         super().__init__()
         S, D = int(num_states), int(dim)
+        if covariance_type not in ("diag", "full"):
+            raise ValueError("GaussianHMM: covariance_type is 'diag' or 'full'")
         if not (1 <= S <= MAX_STATES and 1 <= D <= MAX_DIM):
             raise ValueError(f"GaussianHMM: 1 <= num_states <= {MAX_STATES} and 1 <= dim <= {MAX_DIM} "
                              f"(got {S}, {D})")
+        self.full = covariance_type == "full"
+        if self.full:
+            _full_domain("GaussianHMM", S, D)
+        self.covariance_type = covariance_type
         self.num_states, self.dim = S, D
         self.mixture = False
 
@@ -131,15 +326,39 @@ class GaussianHMM(torch.nn.Module):
         self.log_pi = P(rows(S), requires_grad=False)
         self.log_A = P(rows(S, S), requires_grad=False)
         self.mean = P(torch.randn(S, D, generator=generator, dtype=torch.float64).float(), requires_grad=False)
-        self.log_var = P(torch.zeros(S, D), requires_grad=False)
+        if self.full:
+            self.scale_tril = P(torch.eye(D).repeat(S, 1, 1), requires_grad=False)
+        else:
+            self.log_var = P(torch.zeros(S, D), requires_grad=False)
 
     # ------------------------------------------------------------------ inputs
     def _inputs(self, x, lengths):
         return _check_x("GaussianHMM", self.log_pi, x, lengths, self.dim)
 
     def _params(self):
+        """The four tensors the kernels take: the last is log_var ("diag") or W = L^-1 ("full")."""
+        last = _prec_chol(self.scale_tril) if self.full else self.log_var.detach().contiguous()
         return (self.log_pi.detach().contiguous(), self.log_A.detach().contiguous(),
-                self.mean.detach().contiguous(), self.log_var.detach().contiguous())
+                self.mean.detach().contiguous(), last)
+
+    def _run(self, what, *args):
+        """_estep / _estep_full(what, *args) by the covariance type."""
+        return (_estep_full if self.full else _estep)(what, *args)
+
+    @property
+    def covariances(self):
+        """Sigma (S,D,D) fp32: L L^T ("full") or diag(exp(log_var)) ("diag")."""
+        if self.full:
+            L = self.scale_tril.detach().double().tril()
+            return (L @ L.transpose(1, 2)).float()
+        return torch.diag_embed(torch.exp(self.log_var.detach()))
+
+    @property
+    def precisions_cholesky(self):
+        """W (S,D,D) fp32, lower-triangular with Sigma^-1 = W^T W: what the full kernels are fed."""
+        if self.full:
+            return _prec_chol(self.scale_tril)
+        return torch.diag_embed(torch.exp(-0.5 * self.log_var.detach().double()).float())
 
     def _shift(self, shift):
         if shift is None:
@@ -160,13 +379,15 @@ class GaussianHMM(torch.nn.Module):
     # ------------------------------------------------------- emissions, E-step
     def emission_log_prob(self, x, lengths=None):
         """em (B,T,S) fp32: log N(x[b,t]; mean[s], diag exp(log_var[s])), -inf at t >= length
-        (vqhmm_gauss_emission_f32)."""
+        (vqhmm_gauss_emission_f32); "full": log N(x[b,t]; mean[s], Sigma[s]) (vqhmm_gauss_full_emission_f32)."""
         x, lengths, B, T = self._inputs(x, lengths)
         S, D = self.num_states, self.dim
         em = torch.empty((B, T, S), dtype=torch.float32, device=x.device)
         _, _, mean, log_var = self._params()
+        lib = _ext.load()
+        entry = lib.vqhmm_gauss_full_emission_f32 if self.full else lib.vqhmm_gauss_emission_f32
         with torch.no_grad():
-            _ext.check(_ext.load().vqhmm_gauss_emission_f32(
+            _ext.check(entry(
                 _ext.ptr(mean), _ext.ptr(log_var), _ext.ptr(x), _ext.ptr(lengths), B, T, S, D, _ext.ptr(em),
                 _ext.stream_ptr(x.device)), "GaussianHMM.emission_log_prob")
         return em
@@ -175,25 +396,26 @@ class GaussianHMM(torch.nn.Module):
         """x (B,T,D), lengths (B,), weights (B,) -> dict(pi_cnt (S,), trans_cnt (S,S), occ (S,), m1 (S,D), m2
         (S,D) fp64, loglik (B,) fp32 [, gamma (B,T,S) fp32], shift).  m1 and m2 are the posterior-weighted sums
         of x - shift and (x - shift)^2 (shift (D,), None = 0).  `flat` is the one buffer the counts are views of
-        (all-reduce it across ranks before m_step for data-parallel EM)."""
+        (all-reduce it across ranks before m_step for data-parallel EM).  "full": m2 is (S,D,D), the sums of (x -
+        shift)(x - shift)^T, exactly symmetric."""
         x, lengths, B, T = self._inputs(x, lengths)
-        return _estep("GaussianHMM.e_step", *self._params(), x, lengths, self._shift(shift),
-                      self._weights(weights, B), True, return_gamma)
+        return self._run("GaussianHMM.e_step", *self._params(), x, lengths, self._shift(shift),
+                         self._weights(weights, B), True, return_gamma)
 
     def log_prob(self, x, lengths=None):
         """log p(x[b, :lengths[b]]) (B,) fp32; NaN for length 0 or a non-finite x, -inf if impossible."""
         x, lengths, B, T = self._inputs(x, lengths)
-        return _estep("GaussianHMM.log_prob", *self._params(), x, lengths, None, None, True, False)["loglik"]
+        return self._run("GaussianHMM.log_prob", *self._params(), x, lengths, None, None, True, False)["loglik"]
 
     def posterior(self, x, lengths=None):
         """gamma (B,T,S) fp32: p(z_t = s | x[b, :lengths[b]]), rows at t >= length are 0."""
         x, lengths, B, T = self._inputs(x, lengths)
-        return _estep("GaussianHMM.posterior", *self._params(), x, lengths, None, None, False, True)["gamma"]
+        return self._run("GaussianHMM.posterior", *self._params(), x, lengths, None, None, False, True)["gamma"]
 
     def predict(self, x, lengths=None):
         """The most probable state per position (argmax of gamma) (B,T) int64, -1 at t >= length."""
         x, lengths, B, T = self._inputs(x, lengths)
-        g = _estep("GaussianHMM.predict", *self._params(), x, lengths, None, None, False, True)["gamma"]
+        g = self._run("GaussianHMM.predict", *self._params(), x, lengths, None, None, False, True)["gamma"]
         pad = torch.arange(T, device=x.device).unsqueeze(0) >= lengths.clamp(0, T).unsqueeze(1)
         return g.argmax(-1).masked_fill(pad, -1)
 
@@ -207,11 +429,18 @@ class GaussianHMM(torch.nn.Module):
         return self
 
     @torch.no_grad()
-    def m_step(self, counts, prior_count=0.0, var_floor=1e-6):
+    def m_step(self, counts, prior_count=0.0, var_floor=None, reg_covar=None):
         """Parameters <- the counts' maximiser, in fp64 on the device.  pi and A: row-normalised (counts +
         prior_count), structural zeros kept, a row nothing was counted into keeps its parameters (as CodeHMM).
         mean = shift + m1 / occ, var = max(m2 / occ - (m1 / occ)^2, var_floor); a state with occ = 0 keeps its
-        mean and log_var.  counts["shift"] (None = 0) is the shift its m1 and m2 were taken about."""
+        mean and log_var.  counts["shift"] (None = 0) is the shift its m1 and m2 were taken about.
+        "full": Sigma = m2 / occ - mu mu^T + reg_covar I with mu = m1 / occ (sklearn's regulariser; the third
+        argument is reg_covar), scale_tril = its Cholesky factor; a state with occ = 0, or whose factorisation
+        fails, keeps its mean and scale_tril.  Both default to 1e-6."""
+        if self.full:
+            reg = reg_covar if reg_covar is not None else (1e-6 if var_floor is None else var_floor)
+            return self._m_step_full(counts, prior_count, float(reg))
+        var_floor = 1e-6 if var_floor is None else var_floor
         occ = counts["occ"].to(torch.float64)
         if self.mixture:
             self.log_pi.copy_(CodeHMM._m_rows(occ, self.log_pi, prior_count))
@@ -229,6 +458,30 @@ class GaussianHMM(torch.nn.Module):
         self.mean.copy_(torch.where(live, mu, self.mean.double()).float())
         self.log_var.copy_(torch.where(live, torch.log(var), self.log_var.double()).float())
 
+    def _m_step_full(self, counts, prior_count, reg_covar):
+        occ = counts["occ"].to(torch.float64)
+        if self.mixture:
+            self.log_pi.copy_(CodeHMM._m_rows(occ, self.log_pi, prior_count))
+            self.log_A.copy_(self.log_pi.unsqueeze(0).expand_as(self.log_A))
+        else:
+            self.log_pi.copy_(CodeHMM._m_rows(counts["pi_cnt"], self.log_pi, prior_count))
+            self.log_A.copy_(CodeHMM._m_rows(counts["trans_cnt"], self.log_A, prior_count))
+        D = self.dim
+        o = torch.where(occ > 0, occ, torch.ones_like(occ))
+        mu = counts["m1"].to(torch.float64) / o[:, None]
+        cov = counts["m2"].to(torch.float64) / o[:, None, None] - mu[:, :, None] * mu[:, None, :]
+        cov = cov + reg_covar * torch.eye(D, dtype=torch.float64, device=cov.device)
+        old = self.scale_tril.double().tril()
+        # a state that keeps its parameters is factored from its own covariance (always possible)
+        safe = torch.where((occ > 0)[:, None, None], cov, old @ old.transpose(1, 2))
+        L, ok = _cholesky(torch.where(torch.isfinite(safe), safe, torch.zeros_like(safe)))
+        ok = ok & (occ > 0) & torch.isfinite(cov).all((-1, -2))
+        shift = counts.get("shift")
+        if shift is not None:
+            mu = mu + torch.as_tensor(shift).to(mu.device, torch.float64)
+        self.mean.copy_(torch.where(ok[:, None], mu, self.mean.double()).float())
+        self.scale_tril.copy_(torch.where(ok[:, None, None], L.tril(), old).float())
+
     @torch.no_grad()
     def init_kmeans(self, x, lengths=None, n_iter=10, generator=None):
         """Means from Lloyd's algorithm on the counted positions (Codebook.fit_kmeans), one shared variance from
@@ -243,15 +496,20 @@ class GaussianHMM(torch.nn.Module):
         n = lengths.clamp(0, T).sum().clamp_min(1).double()
         var = (st["sse"] / (D * n)).clamp_min(1e-6)
         self.mean.copy_(cb.weight.detach().float())
-        self.log_var.copy_(torch.log(var).float().expand(S, D))
+        if self.full:   # the same shared spherical covariance
+            self.scale_tril.copy_((torch.sqrt(var) * torch.eye(D, dtype=torch.float64, device=x.device))
+                                  .float().expand(S, D, D))
+        else:
+            self.log_var.copy_(torch.log(var).float().expand(S, D))
 
-    def fit(self, x, lengths=None, n_iter=20, tol=None, prior_count=0.0, var_floor=1e-6, init="kmeans",
-            mixture=False, generator=None):
+    def fit(self, x, lengths=None, n_iter=20, tol=None, prior_count=0.0, var_floor=None, init="kmeans",
+            mixture=False, generator=None, reg_covar=None):
         """Baum-Welch: alternate e_step and m_step.  Returns the total log-likelihoods, one per iteration, each
         under the parameters before that iteration's M-step (0-dim device tensors with tol=None, so the loop has
         no host sync; floats with tol, which stops once the improvement per observed position is < tol).
         init="kmeans" first runs init_kmeans, init=None starts from the current parameters.  The moments are
-        taken about the data mean (computed once).  mixture=True fits the Gaussian mixture (as_mixture)."""
+        taken about the data mean (computed once).  mixture=True fits the Gaussian mixture (as_mixture).
+        var_floor ("diag") and reg_covar ("full") are m_step's, 1e-6 by default."""
         if init not in ("kmeans", None):
             raise ValueError("GaussianHMM.fit: init is 'kmeans' or None")
         x, lengths, B, T = self._inputs(x, lengths)
@@ -265,9 +523,9 @@ class GaussianHMM(torch.nn.Module):
         npos = None
         history = []
         for _ in range(int(n_iter)):
-            st = _estep("GaussianHMM.fit", *self._params(), x, lengths, shift, None, True, False)
+            st = self._run("GaussianHMM.fit", *self._params(), x, lengths, shift, None, True, False)
             total = st["loglik"].double().nansum()
-            self.m_step(st, prior_count, var_floor)
+            self.m_step(st, prior_count, var_floor, reg_covar)
             if tol is None:
                 history.append(total)
                 continue
@@ -295,7 +553,8 @@ class GaussianHMM(torch.nn.Module):
     def sample(self, n, seq_len, generator=None):
         """Ancestral samples -> (states (n, seq_len) int64, x (n, seq_len, D) fp32): the states by inverse CDF from
         torch.rand((n, seq_len), generator=generator), x = mean + exp(log_var / 2) * torch.randn((n, seq_len, D),
-        generator=generator), both drawn on the model's device."""
+        generator=generator), both drawn on the model's device.  "full": the same state draw, then x = mean[z] +
+        scale_tril[z] . normal in torch (one masked matmul per state)."""
         _ext.require_device(self.log_pi)
         n, seq_len = int(n), int(seq_len)
         S, D = self.num_states, self.dim
@@ -304,8 +563,16 @@ class GaussianHMM(torch.nn.Module):
         nr = torch.randn((n, seq_len, D), generator=generator, device=dev, dtype=torch.float32)
         states = torch.empty((n, seq_len), dtype=torch.int32, device=dev)
         x = torch.empty((n, seq_len, D), dtype=torch.float32, device=dev)
+        params = self._params()
+        if self.full:   # the kernel draws the states (its unit-variance x is replaced below)
+            params = params[:3] + (torch.zeros((S, D), dtype=torch.float32, device=dev),)
         with torch.no_grad():
             _ext.check(_ext.load().vqhmm_gauss_sample_f32(
-                *(_ext.ptr(p) for p in self._params()), _ext.ptr(u), _ext.ptr(nr), n, seq_len, S, D,
+                *(_ext.ptr(p) for p in params), _ext.ptr(u), _ext.ptr(nr), n, seq_len, S, D,
                 _ext.ptr(states), _ext.ptr(x), _ext.stream_ptr(dev)), "GaussianHMM.sample")
+            if self.full:
+                L = self.scale_tril.detach().tril()
+                x = self.mean.detach()[states.long()]
+                for s in range(S):
+                    x = x + (states == s).unsqueeze(-1) * (nr @ L[s].T)
         return states.long(), x
