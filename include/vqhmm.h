@@ -459,6 +459,77 @@ int vqhmm_gauss_moments_f32(const float* x, const float* gamma, const int64_t* l
                             double* occ, double* m1, double* m2,
                             void* workspace, size_t ws_bytes, void* stream);
 
+/* ------------------- Gaussian HMM: Viterbi decode and streaming causal filter on x ----
+ * The MAP state path and the causal filter of both Gaussian models (hmm_gauss_decode_dev.h, instantiated
+ * next to the emission code of hmm_gauss.hip and hmm_gauss_full.hip), read from x alone: a wave stages 64
+ * rows of x in LDS, computes their emissions on chip with the function the emission entry uses and runs
+ * the chain on them, the transition matrix in registers.  No (B,T,S) emission table, no expanded log_A
+ * and no xi reaches memory.  Parameters, x, lengths and the limits are the two blocks' above: diagonal
+ * 1 <= S <= 32, 1 <= D <= 64 with log_var (S,D); full 1 <= S <= 32, 1 <= D <= 32, S*D*D <= 8192 with
+ * prec_chol (S,D,D); T <= 2^28, B < 2^31, B*T <= 2^40 (else VQHMM_EUNSUPPORTED, and the workspace query
+ * returns 0).
+ *
+ * vqhmm_gauss_viterbi_f32 / vqhmm_gauss_full_viterbi_f32: path (B,T) int32, score (B) fp32.
+ *   d_0[j] = log_pi[j] + em[0,j],  d_t[j] = (max_i (d_{t-1}[i] + log_A[i,j])) + em[t,j]
+ * in fp32 in exactly this order on the raw log emissions (no max shift), i ascending with a strict >
+ * (ties keep the lowest i); the last state is the first argmax of d_{L-1}, score = d_{L-1}[last];
+ * path[t >= L] = -1 and every element of path is written.  L = 0: path all -1, score = -inf.  A
+ * non-finite x or emission inside the length: path all -1, score = NaN, the other sequences untouched.
+ * An impossible sequence gets what the rule gives: score = -inf and the path of the tie rule.  For
+ * every sequence with finite data the result is bit-identical to vqhmm_viterbi_f32 on log_A[b,t] = log_A
+ * and em as vqhmm_gauss_emission_f32 (vqhmm_gauss_full_emission_f32) writes it.  Workspace:
+ * vqhmm_gauss_viterbi_workspace_size / vqhmm_gauss_full_viterbi_workspace_size (B, T, S, D) bytes: one
+ * backpointer byte per step and state, B * 4*ceil(T/4) * SP with SP = S rounded up to a power of two,
+ * rounded up to 256; the only per-position workspace.
+ *
+ * vqhmm_gauss_filter_f32 / vqhmm_gauss_full_filter_f32: filt (B,T,S) fp32 with filt[b,t,j] = p(z_t = j |
+ * x_{b,0:t}) (rows t < L sum to 1, rows t >= L are 0, every element written), last (B,S) = filt[b, L_b - 1]
+ * and loglik (B) = log p(x_{b,0:L_b} | prev); each of the three is nullable, and with filt NULL nothing of
+ * size B*T*S is written (the streaming / scoring form).  No workspace.  prev (B,S), nullable, is the
+ * filtered distribution at the position just before this chunk (non-negative, need not be normalised):
+ * the distribution before the emission at t = 0 is exp(log_pi) with prev NULL and prev[b] . exp(log_A)
+ * otherwise (log_pi is then not read and may be NULL), so feeding a call's last as the next call's prev
+ * filters a feed chunk by chunk; last may alias prev.  L_b = 0: last[b] = prev[b] (zeros without prev),
+ * loglik = NaN.  An impossible sequence (mass truly 0, or sum(prev[b]) equal to 0 or not finite) gets
+ * loglik = -inf; the first position inside the length whose row of x, or whose emission, is not finite
+ * gives loglik = NaN, and the steps before that position still run; in both cases the rows of filt from
+ * the failing position on, and last, are 0, and the other sequences are untouched.  Numerics are the
+ * E-step's forward: each step uses exp(em_t - max_s em_t), the maxima go into the fp64 log-likelihood
+ * sum, linear probabilities are normalised at every step, four step masses go through one log2 into
+ * fp64, a step whose mass leaves [2^-30, 2^30] is redone max-shifted in natural log.  Accuracy target vs
+ * the fp64 oracle fed the same emissions: |filt|, |last| abs 1e-5, loglik rel 1e-5 of max(1, |loglik|).
+ *
+ * All four: deterministic, graph-capturable, no host sync, 64-bit offsets, every global access inside
+ * its own array (x only at rows t < L; exact-size allocations and pointers misaligned by 4 bytes are
+ * safe).  Return codes, checked in this order on the host before any launch: a negative size ->
+ * VQHMM_EINVAL; S, D or the batch out of range -> VQHMM_EUNSUPPORTED; B = 0 -> VQHMM_OK; B > 0, T = 0 ->
+ * as if every length were 0 (the size-B outputs are written); a null required pointer or a workspace
+ * that is too small -> VQHMM_EINVAL. */
+size_t vqhmm_gauss_viterbi_workspace_size(int64_t B, int64_t T, int64_t S, int64_t D);
+int vqhmm_gauss_viterbi_f32(const float* log_pi, const float* log_A,
+                            const float* mean, const float* log_var,
+                            const float* x, const int64_t* lengths,
+                            int64_t B, int64_t T, int64_t S, int64_t D,
+                            int32_t* path, float* score,
+                            void* workspace, size_t ws_bytes, void* stream);
+int vqhmm_gauss_filter_f32(const float* log_pi, const float* log_A,
+                           const float* mean, const float* log_var,
+                           const float* x, const int64_t* lengths, const float* prev,
+                           int64_t B, int64_t T, int64_t S, int64_t D,
+                           float* filt, float* last, float* loglik, void* stream);
+size_t vqhmm_gauss_full_viterbi_workspace_size(int64_t B, int64_t T, int64_t S, int64_t D);
+int vqhmm_gauss_full_viterbi_f32(const float* log_pi, const float* log_A,
+                                 const float* mean, const float* prec_chol,
+                                 const float* x, const int64_t* lengths,
+                                 int64_t B, int64_t T, int64_t S, int64_t D,
+                                 int32_t* path, float* score,
+                                 void* workspace, size_t ws_bytes, void* stream);
+int vqhmm_gauss_full_filter_f32(const float* log_pi, const float* log_A,
+                                const float* mean, const float* prec_chol,
+                                const float* x, const int64_t* lengths, const float* prev,
+                                int64_t B, int64_t T, int64_t S, int64_t D,
+                                float* filt, float* last, float* loglik, void* stream);
+
 /* -------------------------------------------------- codebook learning ----
  * Per-code statistics of a batch under given assignments, the quantizer's backward from the same
  * pass, and the channels-first lookup (pseudocode.txt:8-32, the codebook's side; vq_codebook.hip).

@@ -30,6 +30,12 @@
     python tools/kbench.py sample --B 512 --T 512 --K 8 --N 64
                                                         (the FFBS and simulation kernels, the filter beside them,
                                                          and a plain-torch FFBS loop on the same shapes)
+    python tools/kbench.py gauss_viterbi --B 2048 --T 200 --K 32 --D 16 [--full] [--old-route]
+    python tools/kbench.py gauss_filter --B 2048 --T 200 --K 32 --D 16 [--full] [--old-route]
+                                                        (GaussianHMM's fused decode / causal filter on x; --full:
+                                                         full covariances; --old-route: also the emission entry +
+                                                         expanded log_A + viterbi / forward_filter; the filter leg
+                                                         also times the E-step of the same shape)
     python tools/kbench.py vq_stats --B 2048 --Dv 64 --T 200 --K 32 [--old-route]
     python tools/kbench.py vq_bwd --B 2048 --Dv 64 --T 200 --K 32 [--old-route]
                                                         (the codebook statistics / the quantizer's fused backward;
@@ -636,6 +642,91 @@ def bench_code_filter(a):
     _bench_code_decode(a, "code_filter")
 
 
+def _bench_gauss_decode(a, leg):
+    """One of GaussianHMM's fused read-outs on x (B,T,--D) at S = --K states, full-length sequences; --full: full
+    covariances.  --old-route: also the time-varying kernels' way to the same result (the emission entry into
+    (B,T,S), log_A expanded to (B,T,S,S), then viterbi / forward_filter; building the tables is part of its
+    time), in five alternating pairs after a warm-up, every pair's two times reported, and a line that checks the
+    two routes agree.  The gauss_filter leg also times the E-step of the same shape in the same pairs: the filter
+    is its forward half and has to stay below it.  Algorithmic HBM bytes per position: x read (4 D) and the
+    backpointers written and read back (2 SP) plus the path (4), or filt (4 S) written."""
+    B, T, S, D = a.B, a.T, a.K, a.D
+    if a.full:
+        hmm, x, L, _ = _full_case(B, T, S, D)
+    else:
+        g = torch.Generator(device="cuda").manual_seed(11)
+        hmm = vqhmm.GaussianHMM(S, D, generator=torch.Generator().manual_seed(3)).cuda()
+        with torch.no_grad():
+            hmm.mean.mul_(2.0)
+        z = torch.randint(0, S, (B, T), device="cuda", generator=g)
+        x = (hmm.mean[z] + torch.randn((B, T, D), device="cuda", generator=g)).contiguous()
+        L = torch.full((B,), T, dtype=torch.int64, device="cuda")
+    log_pi, log_A, mean, par = hmm._params()
+    lib = vqhmm._ext.load()
+    P = vqhmm._ext.ptr
+    st = vqhmm._ext.stream_ptr()
+    pre = "vqhmm_gauss_full_" if a.full else "vqhmm_gauss_"
+    legs = {}
+    if leg == "gauss_viterbi":
+        path = torch.empty(B, T, dtype=torch.int32, device="cuda")
+        score = torch.empty(B, device="cuda")
+        nb = getattr(lib, pre + "viterbi_workspace_size")(B, T, S, D)
+        ws = torch.empty(max(nb, 1), dtype=torch.uint8, device="cuda")
+        entry = getattr(lib, pre + "viterbi_f32")
+
+        def new():
+            entry(P(log_pi), P(log_A), P(mean), P(par), P(x), P(L), B, T, S, D, P(path), P(score), P(ws), nb, st)
+
+        def old():
+            return vqhmm.viterbi(log_pi, log_A.expand(B, T, S, S), hmm.emission_log_prob(x, L), L)
+
+        SP = 1 << max(S - 1, 0).bit_length()
+        byts = B * T * (4 * D + 2 * SP + 4)
+        legs[leg] = new
+    else:
+        filt = torch.empty(B, T, S, device="cuda")
+        last = torch.empty(B, S, device="cuda")
+        ll = torch.empty(B, device="cuda")
+        entry = getattr(lib, pre + "filter_f32")
+
+        def new():
+            entry(P(log_pi), P(log_A), P(mean), P(par), P(x), P(L), None, B, T, S, D, P(filt), P(last), P(ll), st)
+
+        def old():
+            return vqhmm.forward_filter(log_pi, log_A.expand(B, T, S, S), hmm.emission_log_prob(x, L), L)
+
+        def estep():
+            return hmm.log_prob(x, L)
+
+        byts = B * T * (4 * D + 4 * S)
+        legs[leg] = new
+        legs["estep"] = estep
+    if a.old_route:
+        legs["old_route"] = old
+        ref = old()
+        new()
+        torch.cuda.synchronize()
+        if leg == "gauss_viterbi":
+            chk = {"paths_equal": bool(torch.equal(ref[0], path)),
+                   "scores_equal": bool(torch.equal(ref[1].view(torch.int32), score.view(torch.int32)))}
+        else:
+            chk = {"filt_maxdiff": (ref[0] - filt).abs().max().item(),
+                   "loglik_max_rel": ((ref[1] - ll).abs() / ll.abs().clamp(min=1)).max().item()}
+        print(json.dumps({"check": "old_route vs " + leg, "B": B, "T": T, "S": S, "D": D, "full": a.full, **chk}))
+        del ref
+    rounds = _pairs(legs)
+    dims = {"B": B, "T": T, "S": S, "D": D, "full": a.full}
+    _report(legs, rounds, leg, dims, lambda t: {"GBps": byts / t / 1e9, "frac_hbm": byts / t / HBM_PEAK})
+
+
+def bench_gauss_viterbi(a):
+    _bench_gauss_decode(a, "gauss_viterbi")
+
+
+def bench_gauss_filter(a):
+    _bench_gauss_decode(a, "gauss_filter")
+
+
 def _bench_vq_codebook(a, leg):
     """vqhmm_vq_stats_f32 or vqhmm_vq_quantize_bwd_f32 on the argmin's indices of random z.  --old-route: also
     the torch route to the same numbers (vq_stats: bincount + a permuted index_add_ of the residuals in fp64;
@@ -821,10 +912,12 @@ if __name__ == "__main__":
     ap.add_argument("--M", type=int, default=8)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--old-route", action="store_true")
+    ap.add_argument("--full", action="store_true")
     a = ap.parse_args()
     {"vq": bench_vq, "stream": bench_stream, "viterbi": bench_viterbi, "fwdbwd": bench_fwdbwd,
      "filter": bench_filter, "xi": bench_xi, "estep": bench_estep, "estep_batched": bench_estep_batched,
      "gauss_estep": bench_gauss_estep, "gauss_full_estep": bench_gauss_full_estep,
      "gauss_moments": bench_gauss_moments, "code_fit": bench_code_fit, "code_viterbi": bench_code_viterbi,
-     "code_filter": bench_code_filter, "sample": bench_sample, "vq_stats": bench_vq_stats,
+     "code_filter": bench_code_filter, "gauss_viterbi": bench_gauss_viterbi, "gauss_filter": bench_gauss_filter,
+     "sample": bench_sample, "vq_stats": bench_vq_stats,
      "vq_bwd": bench_vq_bwd}[a.what](a)

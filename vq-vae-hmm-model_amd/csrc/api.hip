@@ -545,6 +545,60 @@ int vqhmm_gauss_moments_f32(const float* x, const float* gamma, const int64_t* l
                                   (hipStream_t)stream);
 }
 
+size_t vqhmm_gauss_viterbi_workspace_size(int64_t B, int64_t T, int64_t S, int64_t D) {
+  return hmm_gauss_viterbi_ws_bytes(B, T, S, D);
+}
+
+int vqhmm_gauss_viterbi_f32(const float* log_pi, const float* log_A, const float* mean, const float* log_var,
+                            const float* x, const int64_t* lengths, int64_t B, int64_t T, int64_t S, int64_t D,
+                            int32_t* path, float* score, void* ws, size_t ws_bytes, void* stream) {
+  if (B < 0 || T < 0 || S < 0 || D < 0) return VQHMM_EINVAL;
+  if (!hmm_gauss_supported(S, D)) return VQHMM_EUNSUPPORTED;
+  if (B > 0 && T > 0 &&
+      (!log_pi || !log_A || !mean || !log_var || !x || !lengths || !path || !score || !ws ||
+       ws_bytes < hmm_gauss_viterbi_ws_bytes(B, T, S, D)))
+    return VQHMM_EINVAL;
+  return launch_hmm_gauss_viterbi(log_pi, log_A, mean, log_var, x, lengths, B, T, S, D, path, score, ws,
+                                  (hipStream_t)stream);
+}
+
+int vqhmm_gauss_filter_f32(const float* log_pi, const float* log_A, const float* mean, const float* log_var,
+                           const float* x, const int64_t* lengths, const float* prev, int64_t B, int64_t T,
+                           int64_t S, int64_t D, float* filt, float* last, float* loglik, void* stream) {
+  if (B < 0 || T < 0 || S < 0 || D < 0) return VQHMM_EINVAL;
+  if (!hmm_gauss_supported(S, D)) return VQHMM_EUNSUPPORTED;
+  if (B > 0 && T > 0 && ((!prev && !log_pi) || !log_A || !mean || !log_var || !x || !lengths)) return VQHMM_EINVAL;
+  return launch_hmm_gauss_filter(log_pi, log_A, mean, log_var, x, lengths, prev, B, T, S, D, filt, last, loglik,
+                                 (hipStream_t)stream);
+}
+
+size_t vqhmm_gauss_full_viterbi_workspace_size(int64_t B, int64_t T, int64_t S, int64_t D) {
+  return hmm_gauss_full_viterbi_ws_bytes(B, T, S, D);
+}
+
+int vqhmm_gauss_full_viterbi_f32(const float* log_pi, const float* log_A, const float* mean, const float* prec_chol,
+                                 const float* x, const int64_t* lengths, int64_t B, int64_t T, int64_t S, int64_t D,
+                                 int32_t* path, float* score, void* ws, size_t ws_bytes, void* stream) {
+  if (B < 0 || T < 0 || S < 0 || D < 0) return VQHMM_EINVAL;
+  if (!hmm_gauss_full_supported(S, D)) return VQHMM_EUNSUPPORTED;
+  if (B > 0 && T > 0 &&
+      (!log_pi || !log_A || !mean || !prec_chol || !x || !lengths || !path || !score || !ws ||
+       ws_bytes < hmm_gauss_full_viterbi_ws_bytes(B, T, S, D)))
+    return VQHMM_EINVAL;
+  return launch_hmm_gauss_full_viterbi(log_pi, log_A, mean, prec_chol, x, lengths, B, T, S, D, path, score, ws,
+                                       (hipStream_t)stream);
+}
+
+int vqhmm_gauss_full_filter_f32(const float* log_pi, const float* log_A, const float* mean, const float* prec_chol,
+                                const float* x, const int64_t* lengths, const float* prev, int64_t B, int64_t T,
+                                int64_t S, int64_t D, float* filt, float* last, float* loglik, void* stream) {
+  if (B < 0 || T < 0 || S < 0 || D < 0) return VQHMM_EINVAL;
+  if (!hmm_gauss_full_supported(S, D)) return VQHMM_EUNSUPPORTED;
+  if (B > 0 && T > 0 && ((!prev && !log_pi) || !log_A || !mean || !prec_chol || !x || !lengths)) return VQHMM_EINVAL;
+  return launch_hmm_gauss_full_filter(log_pi, log_A, mean, prec_chol, x, lengths, prev, B, T, S, D, filt, last,
+                                      loglik, (hipStream_t)stream);
+}
+
 size_t vqhmm_vq_stats_workspace_size(int64_t B, int64_t Dv, int64_t T, int64_t K) {
   return vq_codebook_ws_bytes(B, Dv, T, K);
 }

@@ -33,6 +33,10 @@
 //
 // Addressing.  x is read only at rows t < L of the wave's own sequence, parameters only at (s, d) < (S, D), the
 // workspace only inside the sequence's own rows.
+//
+// Decode and filter.  The Viterbi decode and the streaming causal filter on x are hmm_gauss_decode_dev.h's
+// kernels, instantiated at the end of this file on GaussDiagEm (ge_table, ge_stage_x, ge_chunk_em, ge_em), so
+// that their emissions are this file's bits.
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Wunused-function"  // the header's table prologue is not used here
 #include "hmm_code_dev.h"  // the lane helpers and the fast step's range
@@ -688,7 +692,36 @@ int gauss_width(const GaussArgs& a, const GaussPlan& p, hipStream_t s) {
   return gauss_go<1, WT>(a, p, s);
 }
 
+// the decode and filter kernels' view of this file's emissions (hmm_gauss_decode_dev.h): the table is
+// [mu S*D][iv S*D][c S]
+struct GaussDiagEm {
+  __host__ __device__ static int table_floats(int S, int D) { return 2 * S * D + S; }
+  // 4 waves per SIMD up to SP = 16 (<= 128 VGPRs), 3 at SP = 32 (150 and 159)
+  static int cu_waves(int SP) { return SP > 16 ? 12 : 16; }
+  __device__ __forceinline__ static void table(const float* __restrict__ mean, const float* __restrict__ log_var,
+                                               int S, int D, float* tb, int tid, int nthr) {
+    ge_table(mean, log_var, S, D, tb, tb + S * D, tb + 2 * S * D, tid, nthr);
+  }
+  __device__ __forceinline__ static bool stage_x(const float* __restrict__ xg, int n, int D, int DS, int lane,
+                                                 float* xbuf) {
+    return ge_stage_x(xg, n, D, DS, lane, xbuf);
+  }
+  __device__ __forceinline__ static bool chunk_em(const float* xbuf, int DS, const float* tb, int S, int D, int n,
+                                                  int lane, float* ebuf, int ES, float& Mv) {
+    return ge_chunk_em(xbuf, DS, tb, tb + S * D, tb + 2 * S * D, S, D, n, lane, ebuf, ES, Mv);
+  }
+  __device__ __forceinline__ static float em_one(const float* xr, const float* tb, int j, int S, int D) {
+    return ge_em(xr, tb + j * D, tb + S * D + j * D, tb[2 * S * D + j], D);
+  }
+};
+
 }  // namespace
+
+}  // namespace vqhmm
+
+#include "hmm_gauss_decode_dev.h"
+
+namespace vqhmm {
 
 bool hmm_gauss_supported(int64_t S, int64_t D) { return S >= 1 && S <= 32 && D >= 1 && D <= 64; }
 // the batch sizes the launches index (and whose workspace size fits size_t): the query and the launchers agree
@@ -760,6 +793,28 @@ int launch_hmm_gauss_sample(const float* log_pi, const float* log_A, const float
       log_pi, log_A, mean, log_var, uniforms, normals, N, (int)T, (int)S, (int)D, states, x);
   VQHMM_LAUNCH_CHECK();
   return VQHMM_OK;
+}
+
+size_t hmm_gauss_viterbi_ws_bytes(int64_t B, int64_t T, int64_t S, int64_t D) {
+  if (!hmm_gauss_supported(S, D) || B < 0 || T < 0 || !gauss_sizes_ok(B, T)) return 0;
+  return gd_viterbi_ws_bytes(B, T, S);
+}
+
+int launch_hmm_gauss_viterbi(const float* log_pi, const float* log_A, const float* mean, const float* log_var,
+                             const float* x, const int64_t* lengths, int64_t B, int64_t T, int64_t S, int64_t D,
+                             int32_t* path, float* score, void* ws, hipStream_t s) {
+  if (!hmm_gauss_supported(S, D) || !gauss_sizes_ok(B, T)) return VQHMM_EUNSUPPORTED;
+  if (B == 0) return VQHMM_OK;
+  return gd_launch_viterbi<GaussDiagEm>(log_pi, log_A, mean, log_var, x, lengths, B, T, S, D, path, score, ws, s);
+}
+
+int launch_hmm_gauss_filter(const float* log_pi, const float* log_A, const float* mean, const float* log_var,
+                            const float* x, const int64_t* lengths, const float* prev, int64_t B, int64_t T,
+                            int64_t S, int64_t D, float* filt, float* last, float* loglik, hipStream_t s) {
+  if (!hmm_gauss_supported(S, D) || !gauss_sizes_ok(B, T)) return VQHMM_EUNSUPPORTED;
+  if (B == 0) return VQHMM_OK;
+  return gd_launch_filter<GaussDiagEm>(log_pi, log_A, mean, log_var, x, lengths, prev, B, T, S, D, filt, last,
+                                       loglik, s);
 }
 
 }  // namespace vqhmm

@@ -32,6 +32,9 @@
 //
 // Addressing.  x and gamma are read only at rows t < L of the wave's own sequence, parameters only at (s, i, j <=
 // i), the workspace only inside the sequence's own rows.
+//
+// Decode and filter.  hmm_gauss_decode_dev.h's kernels, instantiated at the end of this file on GaussFullEm
+// (gf_table, gf_stage_x, gf_chunk_em, gf_em).
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Wunused-function"  // the header's table prologue is not used here
 #include "hmm_code_dev.h"  // the lane helpers and the fast step's range
@@ -801,7 +804,38 @@ bool gauss_full_sizes_ok(int64_t B, int64_t T) {
   return B <= INT32_MAX && T <= (1 << 28) && (B == 0 || T <= (int64_t(1) << 40) / B);
 }
 
+// the decode and filter kernels' view of this file's emissions (hmm_gauss_decode_dev.h): the table is
+// [W S*P][mu S*D][c S]
+struct GaussFullEm {
+  __host__ __device__ static int table_floats(int S, int D) { return S * gf_tri(D) + S * D + S; }
+  // 4 waves per SIMD up to SP = 8 (<= 128 VGPRs), 3 at SP = 16 (126 and 139), 2 at SP = 32 (171 and 188)
+  static int cu_waves(int SP) { return SP > 16 ? 8 : SP > 8 ? 12 : 16; }
+  __device__ __forceinline__ static void table(const float* __restrict__ mean, const float* __restrict__ prec, int S,
+                                               int D, float* tb, int tid, int nthr) {
+    gf_table(mean, prec, S, D, tb, tb + S * gf_tri(D), tb + S * gf_tri(D) + S * D, tid, nthr);
+  }
+  __device__ __forceinline__ static bool stage_x(const float* __restrict__ xg, int n, int D, int DS, int lane,
+                                                 float* xbuf) {
+    return gf_stage_x(xg, n, D, DS, lane, xbuf);
+  }
+  __device__ __forceinline__ static bool chunk_em(const float* xbuf, int DS, const float* tb, int S, int D, int n,
+                                                  int lane, float* ebuf, int ES, float& Mv) {
+    const int P = gf_tri(D);
+    return gf_chunk_em(xbuf, DS, tb + S * P, tb, tb + S * P + S * D, S, D, n, lane, ebuf, ES, Mv);
+  }
+  __device__ __forceinline__ static float em_one(const float* xr, const float* tb, int j, int S, int D) {
+    const int P = gf_tri(D);
+    return gf_em(xr, tb + S * P + j * D, tb + j * P, tb[S * P + S * D + j], D);
+  }
+};
+
 }  // namespace
+
+}  // namespace vqhmm
+
+#include "hmm_gauss_decode_dev.h"
+
+namespace vqhmm {
 
 bool hmm_gauss_full_supported(int64_t S, int64_t D) {
   return S >= 1 && S <= 32 && D >= 1 && D <= 32 && S * D * D <= GF_MAX_SDD;
@@ -902,6 +936,28 @@ int launch_hmm_gauss_moments(const float* x, const float* gamma, const int64_t* 
                                                                               nullptr, nullptr, occ, m1, m2);
   VQHMM_LAUNCH_CHECK();
   return VQHMM_OK;
+}
+
+size_t hmm_gauss_full_viterbi_ws_bytes(int64_t B, int64_t T, int64_t S, int64_t D) {
+  if (!hmm_gauss_full_supported(S, D) || B < 0 || T < 0 || !gauss_full_sizes_ok(B, T)) return 0;
+  return gd_viterbi_ws_bytes(B, T, S);
+}
+
+int launch_hmm_gauss_full_viterbi(const float* log_pi, const float* log_A, const float* mean, const float* prec_chol,
+                                  const float* x, const int64_t* lengths, int64_t B, int64_t T, int64_t S,
+                                  int64_t D, int32_t* path, float* score, void* ws, hipStream_t s) {
+  if (!hmm_gauss_full_supported(S, D) || !gauss_full_sizes_ok(B, T)) return VQHMM_EUNSUPPORTED;
+  if (B == 0) return VQHMM_OK;
+  return gd_launch_viterbi<GaussFullEm>(log_pi, log_A, mean, prec_chol, x, lengths, B, T, S, D, path, score, ws, s);
+}
+
+int launch_hmm_gauss_full_filter(const float* log_pi, const float* log_A, const float* mean, const float* prec_chol,
+                                 const float* x, const int64_t* lengths, const float* prev, int64_t B, int64_t T,
+                                 int64_t S, int64_t D, float* filt, float* last, float* loglik, hipStream_t s) {
+  if (!hmm_gauss_full_supported(S, D) || !gauss_full_sizes_ok(B, T)) return VQHMM_EUNSUPPORTED;
+  if (B == 0) return VQHMM_OK;
+  return gd_launch_filter<GaussFullEm>(log_pi, log_A, mean, prec_chol, x, lengths, prev, B, T, S, D, filt, last,
+                                       loglik, s);
 }
 
 }  // namespace vqhmm

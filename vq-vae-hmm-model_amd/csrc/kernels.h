@@ -566,6 +566,23 @@ int launch_hmm_gauss_full_estep(const float* log_pi, const float* log_A, const f
 int launch_hmm_gauss_moments(const float* x, const float* gamma, const int64_t* lengths, const float* shift,
                              const float* weights, int64_t B, int64_t T, int64_t S, int64_t D, double* occ,
                              double* m1, double* m2, void* ws, hipStream_t s);
+// ... the MAP path and the causal filter of both Gaussian models on x (hmm_gauss_decode_dev.h, instantiated in
+// hmm_gauss.hip and hmm_gauss_full.hip): path (B,T) / score (B); filt (B,T,S), last (B,S) and loglik (B) nullable,
+// prev (B,S) nullable (then log_pi is not read); ws = the matching *_viterbi_ws_bytes, the filter needs none
+size_t hmm_gauss_viterbi_ws_bytes(int64_t B, int64_t T, int64_t S, int64_t D);
+int launch_hmm_gauss_viterbi(const float* log_pi, const float* log_A, const float* mean, const float* log_var,
+                             const float* x, const int64_t* lengths, int64_t B, int64_t T, int64_t S, int64_t D,
+                             int32_t* path, float* score, void* ws, hipStream_t s);
+int launch_hmm_gauss_filter(const float* log_pi, const float* log_A, const float* mean, const float* log_var,
+                            const float* x, const int64_t* lengths, const float* prev, int64_t B, int64_t T,
+                            int64_t S, int64_t D, float* filt, float* last, float* loglik, hipStream_t s);
+size_t hmm_gauss_full_viterbi_ws_bytes(int64_t B, int64_t T, int64_t S, int64_t D);
+int launch_hmm_gauss_full_viterbi(const float* log_pi, const float* log_A, const float* mean, const float* prec_chol,
+                                  const float* x, const int64_t* lengths, int64_t B, int64_t T, int64_t S,
+                                  int64_t D, int32_t* path, float* score, void* ws, hipStream_t s);
+int launch_hmm_gauss_full_filter(const float* log_pi, const float* log_A, const float* mean, const float* prec_chol,
+                                 const float* x, const int64_t* lengths, const float* prev, int64_t B, int64_t T,
+                                 int64_t S, int64_t D, float* filt, float* last, float* loglik, hipStream_t s);
 // codebook learning (vq_codebook.hip), 1 <= K <= 65536, 1 <= Dv <= 512, K Dv <= 2^21: per-code count / residual
 // sum / sse in fp64 under given assignments (each nullable here), and with dz the quantizer's backward from the
 // same pass (dz = g_zq + *dz_scale r, dcb = *dcb_scale rsum from the reduce launch); ws = vq_codebook_ws_bytes.

@@ -80,6 +80,16 @@ _SIGS = {
     "vqhmm_gauss_moments_workspace_size": (c_sz, [c_i64, c_i64, c_i64, c_i64]),
     "vqhmm_gauss_moments_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp,
                                                c_vp, c_vp, c_sz, c_vp]),
+    "vqhmm_gauss_viterbi_workspace_size": (c_sz, [c_i64, c_i64, c_i64, c_i64]),
+    "vqhmm_gauss_viterbi_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp,
+                                               c_vp, c_vp, c_sz, c_vp]),
+    "vqhmm_gauss_filter_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64,
+                                              c_vp, c_vp, c_vp, c_vp]),
+    "vqhmm_gauss_full_viterbi_workspace_size": (c_sz, [c_i64, c_i64, c_i64, c_i64]),
+    "vqhmm_gauss_full_viterbi_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64,
+                                                    c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "vqhmm_gauss_full_filter_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64,
+                                                   c_i64, c_vp, c_vp, c_vp, c_vp]),
     "vqhmm_vq_stats_workspace_size": (c_sz, [c_i64, c_i64, c_i64, c_i64]),
     "vqhmm_vq_stats_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp,
                                           c_sz, c_vp]),

@@ -11,6 +11,10 @@ kernels of hmm_gauss_full.hip (vqhmm_gauss_full_emission_f32 / vqhmm_gauss_full_
 return the S x D x D second moments; the M-step adds sklearn's reg_covar to the diagonal and factors in fp64 on the
 device.  `gauss_full_log_prob` is its differentiable log-likelihood, `regime_moments` / `regime_covariance` the
 same moments under a caller-supplied posterior (vqhmm_gauss_moments_f32).
+
+Read-outs of a fitted model, both covariance types, fused on x (no emission table, no expanded log_A): `decode`
+(the MAP regime path, vqhmm_gauss_viterbi_f32 / vqhmm_gauss_full_viterbi_f32), `filter` / `update` (the causal
+filter with a carried (B,S) state, vqhmm_gauss_filter_f32 / vqhmm_gauss_full_filter_f32) and `predict_next`.
 """
 import torch
 
@@ -418,6 +422,84 @@ class GaussianHMM(torch.nn.Module):
         g = self._run("GaussianHMM.predict", *self._params(), x, lengths, None, None, False, True)["gamma"]
         pad = torch.arange(T, device=x.device).unsqueeze(0) >= lengths.clamp(0, T).unsqueeze(1)
         return g.argmax(-1).masked_fill(pad, -1)
+
+    # ------------------------------------------------------- decode and filter
+    def decode(self, x, lengths=None):
+        """MAP state path (Viterbi on x, vqhmm_gauss_viterbi_f32 / vqhmm_gauss_full_viterbi_f32) -> (path (B,T)
+        int32 with -1 at t >= length, score (B,) fp32 = the path's log weight).  Length 0: score -inf; a
+        non-finite x or emission inside the length: path all -1 and score NaN."""
+        x, lengths, B, T = self._inputs(x, lengths)
+        S, D = self.num_states, self.dim
+        dev = x.device
+        path = torch.empty((B, T), dtype=torch.int32, device=dev)
+        score = torch.empty((B,), dtype=torch.float32, device=dev)
+        lib = _ext.load()
+        size, entry = ((lib.vqhmm_gauss_full_viterbi_workspace_size, lib.vqhmm_gauss_full_viterbi_f32) if self.full
+                       else (lib.vqhmm_gauss_viterbi_workspace_size, lib.vqhmm_gauss_viterbi_f32))
+        nb = size(B, T, S, D)
+        ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=dev)
+        with torch.no_grad():
+            _ext.check(entry(*(_ext.ptr(p) for p in self._params()), _ext.ptr(x), _ext.ptr(lengths), B, T, S, D,
+                             _ext.ptr(path), _ext.ptr(score), _ext.ptr(ws), nb, _ext.stream_ptr(dev)),
+                       "GaussianHMM.decode")
+        return path, score
+
+    def _filter(self, x, lengths, state, want_filt):
+        x, lengths, B, T = self._inputs(x, lengths)
+        S, D = self.num_states, self.dim
+        dev = x.device
+        if state is not None:
+            if not torch.is_tensor(state) or state.shape != (B, S) or state.dtype != torch.float32:
+                raise ValueError(f"GaussianHMM: state must be a ({B}, {S}) float32 tensor")
+            _ext.require_device(state)
+            state = state.contiguous()
+        filt = torch.empty((B, T, S), dtype=torch.float32, device=dev) if want_filt else None
+        last = torch.empty((B, S), dtype=torch.float32, device=dev)
+        loglik = torch.empty((B,), dtype=torch.float32, device=dev)
+        lib = _ext.load()
+        entry = lib.vqhmm_gauss_full_filter_f32 if self.full else lib.vqhmm_gauss_filter_f32
+        with torch.no_grad():
+            _ext.check(entry(*(_ext.ptr(p) for p in self._params()), _ext.ptr(x), _ext.ptr(lengths), _ext.ptr(state),
+                             B, T, S, D, _ext.ptr(filt), _ext.ptr(last), _ext.ptr(loglik), _ext.stream_ptr(dev)),
+                       "GaussianHMM.filter")
+        return filt, last, loglik
+
+    def filter(self, x, lengths=None, state=None, return_state=False):
+        """Causal filter (vqhmm_gauss_filter_f32 / vqhmm_gauss_full_filter_f32): filt (B,T,S) fp32 with filt[b,t] =
+        p(z_t | x[b, :t+1]) (no look-ahead; rows at t >= length are 0) and loglik (B,) = log p(x[b, :length] |
+        state).  `state` (B,S) fp32 is the carry of the previous chunk (None: the sequence starts from log_pi);
+        with return_state the new carry filt[b, length-1] is returned too, and feeding it back gives what one
+        call on the concatenated observations gives.  loglik is NaN for length 0 (the carry then passes
+        through)."""
+        filt, last, loglik = self._filter(x, lengths, state, True)
+        return (filt, loglik, last) if return_state else (filt, loglik)
+
+    def update(self, x, lengths=None, state=None):
+        """The streaming form of `filter`: -> (state (B,S), loglik (B,)) without writing filt."""
+        _, last, loglik = self._filter(x, lengths, state, False)
+        return last, loglik
+
+    @torch.no_grad()
+    def predict_next(self, state):
+        """The next observation's predictive regime distribution, mean and covariance from a filtered state (B,S)
+        -> (probs (B,S), mean (B,D), cov (B,D,D)) fp32: probs = normalise(state exp(log_A)), mean = probs . mu,
+        cov = sum_s probs_s (Sigma_s + mu_s mu_s^T) - mean mean^T, in fp64 on the device."""
+        S = self.num_states
+        if not torch.is_tensor(state) or state.dim() != 2 or state.shape[1] != S or state.dtype != torch.float32:
+            raise ValueError(f"GaussianHMM: state must be a (B, {S}) float32 tensor")
+        _ext.require_device(self.log_pi, state)
+        nxt = state.double() @ torch.exp(self.log_A.detach().double())
+        probs = nxt / nxt.sum(-1, keepdim=True)
+        mu = self.mean.detach().double()
+        if self.full:
+            L = self.scale_tril.detach().double().tril()
+            sigma = L @ L.transpose(1, 2)
+        else:
+            sigma = torch.diag_embed(torch.exp(self.log_var.detach().double()))
+        mean = probs @ mu
+        second = (sigma + mu[:, :, None] * mu[:, None, :]).reshape(S, -1)
+        cov = (probs @ second).view(-1, self.dim, self.dim) - mean[:, :, None] * mean[:, None, :]
+        return probs.float(), mean.float(), cov.float()
 
     # ----------------------------------------------------------------- M-step
     @torch.no_grad()
