@@ -369,6 +369,28 @@ int vqhmm_code_sample_f32(const float* log_pi, const float* log_A, const float* 
  * Accuracy target vs the fp64 oracle fed the same emissions, per position: |gamma| abs 1e-5, |xi| abs
  * 2e-5, loglik rel 1e-5 of max(1, |loglik|); m1 and m2 2e-5 of sum |x - shift| and sum (x - shift)^2.
  *
+ * vqhmm_gauss_estep_batched_f32: the same E-step for a stack of M models (EM restarts, members of
+ * different state counts padded with -inf, the components of a mixture) on one shared (x, lengths,
+ * shift): log_pi (M,S), log_A (M,S,S), mean (M,S,D), log_var (M,S,D) in, pi_cnt (M,S), trans_cnt
+ * (M,S,S), occ (M,S), m1 (M,S,D), m2 (M,S,D) fp64, loglik (M,B) and gamma (M,B,T,S) (both nullable)
+ * out, all contiguous, the member slices only 4-byte aligned (the addressing guarantee above holds per
+ * member).  The member is a grid dimension of the same two kernels: the call is two launches whatever
+ * M is, each member runs the single model's schedule (which depends on B, T, S, D only), and member
+ * m's outputs are bit-identical to vqhmm_gauss_estep_f32 on member m's slices (which is the M = 1 case
+ * of it).  weights (M,B) fp32, nullable (= all 1): member m's counts are sum_b weights[m,b] *
+ * (sequence b's counts under member m), the product taken in fp64 as one fma where the contribution is
+ * added, so all-ones weights give the bits of weights = NULL.  Weights may be negative or 0 and must
+ * be finite (a non-finite weight leaves that member's counts unspecified, the other members'
+ * untouched); loglik and gamma do not depend on them.  The failure rules are per member: a sequence
+ * of length 0, or that is impossible or meets a non-finite x or emission under member m, contributes
+ * exactly 0 to member m, has zero gamma rows there and contributes normally to the others; under a
+ * member whose own parameters are degenerate (a NaN log_var) every loglik is NaN and every count 0,
+ * and its neighbours are bit-identical to the call without it.  1 <= M <= 65535, else
+ * VQHMM_EUNSUPPORTED (and the workspace query returns 0); M < 0 -> VQHMM_EINVAL.  B*T == 0: as above,
+ * per member.  Workspace: vqhmm_gauss_estep_batched_workspace_size(B, T, S, D, M) bytes = M
+ * single-model workspaces (each rounded up to 256 bytes).  Each member stages x again.  Deterministic,
+ * no float atomics, graph-capturable, no host sync, 64-bit offsets.
+ *
  * vqhmm_gauss_sample_f32: ancestral sampling of N sequences of length T.  uniforms (N,T) fp32 in
  * [0,1) draw z_t by vqhmm_code_sample_f32's inverse-CDF rule (from pi at t = 0, from row z_{t-1} of A
  * afterwards); x[n,t,d] = fmaf(sd, normals[n,t,d], mean[z_t,d]) with sd = exp(log_var[z_t,d] / 2)
@@ -393,6 +415,15 @@ int vqhmm_gauss_estep_f32(const float* log_pi, const float* log_A,
                           double* pi_cnt, double* trans_cnt, double* occ, double* m1, double* m2,
                           float* loglik, float* gamma,
                           void* workspace, size_t ws_bytes, void* stream);
+size_t vqhmm_gauss_estep_batched_workspace_size(int64_t B, int64_t T, int64_t S, int64_t D, int64_t M);
+int vqhmm_gauss_estep_batched_f32(const float* log_pi, const float* log_A,
+                                  const float* mean, const float* log_var,
+                                  const float* x, const int64_t* lengths,
+                                  const float* shift, const float* weights,
+                                  int64_t B, int64_t T, int64_t S, int64_t D, int64_t M,
+                                  double* pi_cnt, double* trans_cnt, double* occ, double* m1, double* m2,
+                                  float* loglik, float* gamma,
+                                  void* workspace, size_t ws_bytes, void* stream);
 int vqhmm_gauss_sample_f32(const float* log_pi, const float* log_A,
                            const float* mean, const float* log_var,
                            const float* uniforms, const float* normals,
@@ -428,6 +459,14 @@ int vqhmm_gauss_sample_f32(const float* log_pi, const float* log_A,
  * buffers, and the accuracy targets, with m2[s,i,j] within 2e-5 of sum |x_i - shift_i| |x_j - shift_j|.
  * Workspace: vqhmm_gauss_full_estep_workspace_size(B, T, S, D) bytes.
  *
+ * vqhmm_gauss_full_estep_batched_f32: vqhmm_gauss_estep_batched_f32 with these emissions, word for
+ * word: prec_chol (M,S,D,D) in, m2 (M,S,D,D) out, the other arrays as there; two launches whatever M
+ * is; member m bit-identical to vqhmm_gauss_full_estep_f32 on its slices (the M = 1 case); weights
+ * (M,B); per-member failure rules (a member with a non-positive prec_chol diagonal has every loglik
+ * NaN and every count 0, its neighbours untouched); 1 <= M <= 65535.  Workspace:
+ * vqhmm_gauss_full_estep_batched_workspace_size(B, T, S, D, M) bytes = M single-model workspaces (each
+ * rounded up to 256 bytes).
+ *
  * vqhmm_gauss_moments_f32: occ (S), m1 (S,D) and m2 (S,D,D) as above, under a caller-supplied gamma
  * (B,T,S) fp32 (an encoder's posterior, a filter's output) in place of the chain's: the per-regime
  * weighted sums behind a pooled regime mean and covariance.  gamma at t >= length is never read.  A
@@ -452,6 +491,15 @@ int vqhmm_gauss_full_estep_f32(const float* log_pi, const float* log_A,
                                double* pi_cnt, double* trans_cnt, double* occ, double* m1, double* m2,
                                float* loglik, float* gamma,
                                void* workspace, size_t ws_bytes, void* stream);
+size_t vqhmm_gauss_full_estep_batched_workspace_size(int64_t B, int64_t T, int64_t S, int64_t D, int64_t M);
+int vqhmm_gauss_full_estep_batched_f32(const float* log_pi, const float* log_A,
+                                       const float* mean, const float* prec_chol,
+                                       const float* x, const int64_t* lengths,
+                                       const float* shift, const float* weights,
+                                       int64_t B, int64_t T, int64_t S, int64_t D, int64_t M,
+                                       double* pi_cnt, double* trans_cnt, double* occ, double* m1, double* m2,
+                                       float* loglik, float* gamma,
+                                       void* workspace, size_t ws_bytes, void* stream);
 size_t vqhmm_gauss_moments_workspace_size(int64_t B, int64_t T, int64_t S, int64_t D);
 int vqhmm_gauss_moments_f32(const float* x, const float* gamma, const int64_t* lengths,
                             const float* shift, const float* weights,

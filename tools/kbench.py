@@ -20,6 +20,11 @@
                                                          gamma; --old-route: also the torch route (triangular solve,
                                                          emissions, expanded log_A, pairwise_posteriors, fp64 einsum /
                                                          the fp64 einsum alone), five alternating pairs, a check line)
+    python tools/kbench.py gauss_estep_batched --B 512 --T 512 --K 8 --D 5 --M 8 [--full] [--old-route]
+                                                        (M Gaussian HMMs in one vqhmm_gauss_estep_batched_f32 /
+                                                         vqhmm_gauss_full_estep_batched_f32 call; --old-route: also M
+                                                         sequential single-model calls on the members, five alternating
+                                                         pairs; every member is first checked bit for bit against them)
     python tools/kbench.py code_fit --B 256 --T 200 --K 8 --V 512 --M 8 [--iters 20]
                                                         (--iters EM iterations of CodeHMMEnsemble.fit against --M
                                                          sequential CodeHMM.fit(n_init=1) runs, five alternating pairs)
@@ -484,6 +489,74 @@ def bench_gauss_full_estep(a):
             lambda t: {"GBps": byts / t / 1e9, "frac_hbm": byts / t / HBM_PEAK})
 
 
+def bench_gauss_estep_batched(a):
+    """vqhmm_gauss_estep_batched_f32 (--full: vqhmm_gauss_full_estep_batched_f32; counts + loglik, no gamma) on --M
+    members of S = --K states that share x (B,T,--D), full lengths and the shift.  Before any timing every member's
+    five counts and loglik are compared byte for byte with the single-model call on its slices (a check line;
+    a mismatch ends the run).  --old-route: also --M sequential single-model calls, the only other way to the same
+    numbers, in five alternating pairs after a warm-up, every pair's two times reported."""
+    B, T, S, D, M, full = a.B, a.T, a.K, a.D, a.M, a.full
+    gen = torch.Generator().manual_seed(3)
+    ens = vqhmm.GaussianHMMEnsemble(num_models=M, num_states=S, dim=D, covariance_type="full" if full else "diag",
+                                    generator=gen).cuda()
+    g = torch.Generator(device="cuda").manual_seed(11)
+    with torch.no_grad():
+        ens.mean.mul_(2.0)
+        if full:
+            Lc = torch.randn((M, S, D, D), device="cuda", generator=g).tril(-1) * (0.4 / math.sqrt(D))
+            ens.scale_tril.copy_(Lc + torch.diag_embed(torch.rand((M, S, D), device="cuda", generator=g) + 0.6))
+    z = torch.randint(0, S, (B, T), device="cuda", generator=g)
+    x = (ens.mean[0][z] + torch.randn((B, T, D), device="cuda", generator=g)).contiguous()
+    L = torch.full((B,), T, dtype=torch.int64, device="cuda")
+    shift = x.mean((0, 1)).contiguous()
+    log_pi, log_A, mean, last = (t.contiguous() for t in ens._params())
+    lib = vqhmm._ext.load()
+    P = vqhmm._ext.ptr
+    st = vqhmm._ext.stream_ptr()
+    sizes = (S, S * S, S, S * D, S * D * D if full else S * D)
+    cnt = [torch.empty((M, n), dtype=torch.float64, device="cuda") for n in sizes]
+    cnt1 = [torch.empty((M, n), dtype=torch.float64, device="cuda") for n in sizes]
+    ll, ll1 = torch.empty(M, B, device="cuda"), torch.empty(M, B, device="cuda")
+    if full:
+        size_m, entry_m = lib.vqhmm_gauss_full_estep_batched_workspace_size, lib.vqhmm_gauss_full_estep_batched_f32
+        size_1, entry_1 = lib.vqhmm_gauss_full_estep_workspace_size, lib.vqhmm_gauss_full_estep_f32
+    else:
+        size_m, entry_m = lib.vqhmm_gauss_estep_batched_workspace_size, lib.vqhmm_gauss_estep_batched_f32
+        size_1, entry_1 = lib.vqhmm_gauss_estep_workspace_size, lib.vqhmm_gauss_estep_f32
+    nb, nb1 = size_m(B, T, S, D, M), size_1(B, T, S, D)
+    ws = torch.empty(max(nb, 1), dtype=torch.uint8, device="cuda")
+
+    def new():
+        entry_m(P(log_pi), P(log_A), P(mean), P(last), P(x), P(L), P(shift), None, B, T, S, D, M,
+                *(P(c) for c in cnt), P(ll), None, P(ws), nb, st)
+
+    def old():
+        for m in range(M):
+            entry_1(P(log_pi[m]), P(log_A[m]), P(mean[m]), P(last[m]), P(x), P(L), P(shift), None, B, T, S, D,
+                    *(P(c[m]) for c in cnt1), P(ll1[m]), None, P(ws), nb1, st)
+
+    new()
+    old()
+    torch.cuda.synchronize()
+    same = all(torch.equal(u.view(torch.uint8), v.view(torch.uint8)) for u, v in zip(cnt + [ll], cnt1 + [ll1]))
+    dims = {"B": B, "T": T, "S": S, "D": D, "M": M, "full": bool(full)}
+    print(json.dumps(dict({"check": "sequential vs gauss_estep_batched", "bit_identical": same}, **dims)))
+    if not same:
+        raise SystemExit("gauss_estep_batched: a member differs from the single-model call")
+    legs = {"gauss_estep_batched": new}
+    if a.old_route:
+        legs["sequential"] = old
+    rounds = _pairs(legs)
+    t = {k: sorted(v)[len(v) // 2] for k, v in rounds.items()}
+    for k in legs:
+        rec = dict({"kernel": k}, **dims, us=t[k] * 1e6, pairs_us=[r * 1e6 for r in rounds[k]],
+                   us_per_member=t[k] * 1e6 / M)
+        if k == "sequential":
+            rec["x_gauss_estep_batched"] = t[k] / t["gauss_estep_batched"]
+            rec["batched_faster_in_every_pair"] = all(o > f for o, f in zip(rounds[k], rounds["gauss_estep_batched"]))
+        print(json.dumps(rec))
+
+
 def bench_gauss_moments(a):
     """vqhmm_gauss_moments_f32 (occ, m1, m2 under a given gamma (B,T,--K)) on x (B,T,--D).  --old-route: also the
     fp64 einsum of the same sums, in five alternating pairs, and a check line."""
@@ -917,6 +990,7 @@ if __name__ == "__main__":
     {"vq": bench_vq, "stream": bench_stream, "viterbi": bench_viterbi, "fwdbwd": bench_fwdbwd,
      "filter": bench_filter, "xi": bench_xi, "estep": bench_estep, "estep_batched": bench_estep_batched,
      "gauss_estep": bench_gauss_estep, "gauss_full_estep": bench_gauss_full_estep,
+     "gauss_estep_batched": bench_gauss_estep_batched,
      "gauss_moments": bench_gauss_moments, "code_fit": bench_code_fit, "code_viterbi": bench_code_viterbi,
      "code_filter": bench_code_filter, "gauss_viterbi": bench_gauss_viterbi, "gauss_filter": bench_gauss_filter,
      "sample": bench_sample, "vq_stats": bench_vq_stats,

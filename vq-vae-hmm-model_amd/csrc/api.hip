@@ -490,6 +490,25 @@ int vqhmm_gauss_estep_f32(const float* log_pi, const float* log_A, const float* 
                                 trans_cnt, occ, m1, m2, loglik, gamma, ws, (hipStream_t)stream);
 }
 
+size_t vqhmm_gauss_estep_batched_workspace_size(int64_t B, int64_t T, int64_t S, int64_t D, int64_t M) {
+  return hmm_gauss_estep_batched_ws_bytes(B, T, S, D, M);
+}
+
+int vqhmm_gauss_estep_batched_f32(const float* log_pi, const float* log_A, const float* mean, const float* log_var,
+                                  const float* x, const int64_t* lengths, const float* shift, const float* weights,
+                                  int64_t B, int64_t T, int64_t S, int64_t D, int64_t M, double* pi_cnt,
+                                  double* trans_cnt, double* occ, double* m1, double* m2, float* loglik,
+                                  float* gamma, void* ws, size_t ws_bytes, void* stream) {
+  if (B < 0 || T < 0 || S < 0 || D < 0 || M < 0) return VQHMM_EINVAL;
+  if (!hmm_gauss_supported(S, D) || !hmm_code_members_supported(M)) return VQHMM_EUNSUPPORTED;
+  if (!pi_cnt || !trans_cnt || !occ || !m1 || !m2) return VQHMM_EINVAL;  // written whatever B and T are
+  if (B * T > 0 && (!log_pi || !log_A || !mean || !log_var || !x || !lengths || !ws ||
+                    ws_bytes < hmm_gauss_estep_batched_ws_bytes(B, T, S, D, M)))
+    return VQHMM_EINVAL;
+  return launch_hmm_gauss_estep_batched(log_pi, log_A, mean, log_var, x, lengths, shift, weights, B, T, S, D, M,
+                                        pi_cnt, trans_cnt, occ, m1, m2, loglik, gamma, ws, (hipStream_t)stream);
+}
+
 int vqhmm_gauss_sample_f32(const float* log_pi, const float* log_A, const float* mean, const float* log_var,
                            const float* uniforms, const float* normals, int64_t N, int64_t T, int64_t S, int64_t D,
                            int32_t* states, float* x, void* stream) {
@@ -527,6 +546,27 @@ int vqhmm_gauss_full_estep_f32(const float* log_pi, const float* log_A, const fl
     return VQHMM_EINVAL;
   return launch_hmm_gauss_full_estep(log_pi, log_A, mean, prec_chol, x, lengths, shift, weights, B, T, S, D, pi_cnt,
                                      trans_cnt, occ, m1, m2, loglik, gamma, ws, (hipStream_t)stream);
+}
+
+size_t vqhmm_gauss_full_estep_batched_workspace_size(int64_t B, int64_t T, int64_t S, int64_t D, int64_t M) {
+  return hmm_gauss_full_estep_batched_ws_bytes(B, T, S, D, M);
+}
+
+int vqhmm_gauss_full_estep_batched_f32(const float* log_pi, const float* log_A, const float* mean,
+                                       const float* prec_chol, const float* x, const int64_t* lengths,
+                                       const float* shift, const float* weights, int64_t B, int64_t T, int64_t S,
+                                       int64_t D, int64_t M, double* pi_cnt, double* trans_cnt, double* occ,
+                                       double* m1, double* m2, float* loglik, float* gamma, void* ws,
+                                       size_t ws_bytes, void* stream) {
+  if (B < 0 || T < 0 || S < 0 || D < 0 || M < 0) return VQHMM_EINVAL;
+  if (!hmm_gauss_full_supported(S, D) || !hmm_code_members_supported(M)) return VQHMM_EUNSUPPORTED;
+  if (!pi_cnt || !trans_cnt || !occ || !m1 || !m2) return VQHMM_EINVAL;  // written whatever B and T are
+  if (B * T > 0 && (!log_pi || !log_A || !mean || !prec_chol || !x || !lengths || !ws ||
+                    ws_bytes < hmm_gauss_full_estep_batched_ws_bytes(B, T, S, D, M)))
+    return VQHMM_EINVAL;
+  return launch_hmm_gauss_full_estep_batched(log_pi, log_A, mean, prec_chol, x, lengths, shift, weights, B, T, S, D,
+                                             M, pi_cnt, trans_cnt, occ, m1, m2, loglik, gamma, ws,
+                                             (hipStream_t)stream);
 }
 
 size_t vqhmm_gauss_moments_workspace_size(int64_t B, int64_t T, int64_t S, int64_t D) {

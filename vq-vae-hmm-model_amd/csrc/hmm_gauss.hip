@@ -31,6 +31,11 @@
 // slabs in wave order into its partial, a second launch sums the partials in a fixed order: no atomics, the same
 // bits run to run.  Sequences are assigned statically (wave w of workgroup g takes b = g NW + w, then strides).
 //
+// Members.  blockIdx.y is the member of a stack of M models that share x, lengths and shift (the batched entry; the
+// single-model entry is M = 1), as in hmm_code.hip: a member has its own parameter slices, weights row, alpha rows,
+// partials (`mstride` workspace bytes apart) and output blocks, and runs exactly the single model's plan, so its
+// bits are the single-model call's.  Each member stages x again.
+//
 // Addressing.  x is read only at rows t < L of the wave's own sequence, parameters only at (s, d) < (S, D), the
 // workspace only inside the sequence's own rows.
 //
@@ -131,14 +136,29 @@ struct GaussArgs {
   const float* x;
   const int64_t* lengths;
   const float* shift;    // (D), nullable (= 0)
-  const float* weights;  // (B), nullable (= all 1)
+  const float* weights;  // (M, B), nullable (= all 1)
   int64_t B;
   int T, S, D;
   float* alpha;   // (B, T, S) scaled forward vectors
   double* part;   // [gridDim.x][m1 S*D | m2 S*D | trans S*S | pi S | occ S]
   float* loglik;  // nullable
   float* gamma;   // nullable
+  size_t mstride;  // bytes from a member's alpha / part to the next member's
 };
+
+// member m's view of the arguments (m = 0 changes nothing): x, lengths and shift are shared
+__device__ __forceinline__ GaussArgs gauss_member(GaussArgs a, int64_t m) {
+  a.log_pi += m * a.S;
+  a.log_A += m * a.S * a.S;
+  a.mean += m * a.S * a.D;
+  a.log_var += m * a.S * a.D;
+  if (a.weights) a.weights += m * a.B;
+  a.alpha = reinterpret_cast<float*>(reinterpret_cast<char*>(a.alpha) + m * a.mstride);
+  a.part = reinterpret_cast<double*>(reinterpret_cast<char*>(a.part) + m * a.mstride);
+  if (a.loglik) a.loglik += m * a.B;
+  if (a.gamma) a.gamma += m * a.B * (int64_t)a.T * a.S;
+  return a;
+}
 
 // ------------------------------------------------------------------------------ emission entry
 // one chunk of 64 rows per wave; LDS: [mu S*D][iv S*D][c S] [per wave: xbuf 64*DS, obuf 64*OS]
@@ -192,8 +212,9 @@ __global__ __launch_bounds__(256) void gauss_emission_kernel(const float* __rest
 // out = sum over the partials in a fixed order (code_reduce_kernel's scheme): 16 elements per workgroup, thread
 // (py, kx) adds partials py, py + 16, .. of element kx in index order, then the 16 sums are added in py order
 constexpr int GE_RK = 16, GE_RP = 16;
-__global__ __launch_bounds__(GE_RK* GE_RP) void gauss_reduce_kernel(const double* __restrict__ part, int np, int S,
-                                                                    int D, double* __restrict__ pi_cnt,
+__global__ __launch_bounds__(GE_RK* GE_RP) void gauss_reduce_kernel(const double* __restrict__ part,
+                                                                    size_t mstride, int np, int S, int D,
+                                                                    double* __restrict__ pi_cnt,
                                                                     double* __restrict__ trans_cnt,
                                                                     double* __restrict__ occ,
                                                                     double* __restrict__ m1,
@@ -202,6 +223,13 @@ __global__ __launch_bounds__(GE_RK* GE_RP) void gauss_reduce_kernel(const double
   const int SD = S * D, SS = S * S, NE = 2 * SD + SS + 2 * S;
   const int kx = threadIdx.x % GE_RK, py = threadIdx.x / GE_RK;
   const int k = (int)blockIdx.x * GE_RK + kx;
+  const int64_t mem = blockIdx.y;  // member: its own partials (mstride bytes apart) and output blocks
+  part = reinterpret_cast<const double*>(reinterpret_cast<const char*>(part) + mem * mstride);
+  pi_cnt += mem * S;
+  trans_cnt += mem * SS;
+  occ += mem * S;
+  m1 += mem * SD;
+  m2 += mem * SD;
   double acc = 0.0;
   if (k < NE) {
 #pragma unroll 4
@@ -226,10 +254,12 @@ __global__ __launch_bounds__(GE_RK* GE_RP) void gauss_reduce_kernel(const double
   }
 }
 
-// WT: the call has weights; without them every weighted add is the plain fp64 add (hmm_code.hip)
-template <int SP, bool WT>
-__global__ __launch_bounds__(256) void gauss_estep_kernel(const GaussArgs a) {
+// WT: the call has weights; without them every weighted add is the plain fp64 add (hmm_code.hip).  MEM: the launch
+// has more than one member (blockIdx.y); with one the arguments stay kernel arguments, as in hmm_code.hip
+template <int SP, bool WT, bool MEM>
+__global__ __launch_bounds__(256) void gauss_estep_kernel(const GaussArgs a0) {
   extern __shared__ double ge_smem[];
+  const GaussArgs a = MEM ? gauss_member(a0, blockIdx.y) : a0;
   constexpr int ES = SP | 1;  // row stride of the chunk's emission buffer (odd: the lane = time pass is conflict-free)
   const int S = a.S, D = a.D, T = a.T;
   const int SD = S * D, NT = S * S + 2 * S, DS = ge_odd(D);
@@ -670,26 +700,26 @@ GaussPlan gauss_plan(int64_t B, int64_t T, int64_t S, int64_t D) {
   return p;
 }
 
-template <int SP, bool WT>
-int gauss_go(const GaussArgs& a, const GaussPlan& p, hipStream_t s) {
-  auto kern = gauss_estep_kernel<SP, WT>;
+template <int SP, bool WT, bool MEM>
+int gauss_go(const GaussArgs& a, const GaussPlan& p, int64_t M, hipStream_t s) {
+  auto kern = gauss_estep_kernel<SP, WT, MEM>;
   // more than 64 KB of dynamic LDS has to be asked for, once per kernel
   static const hipError_t big_lds = hipFuncSetAttribute(
       reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)GE_LDS_MAX);
   (void)big_lds;
-  kern<<<(unsigned)p.nblk, 64 * p.nw, p.lds_bytes, s>>>(a);
+  kern<<<dim3((unsigned)p.nblk, (unsigned)M), 64 * p.nw, p.lds_bytes, s>>>(a);
   VQHMM_LAUNCH_CHECK();
   return VQHMM_OK;
 }
 
-template <bool WT>
-int gauss_width(const GaussArgs& a, const GaussPlan& p, hipStream_t s) {
-  if (a.S > 16) return gauss_go<32, WT>(a, p, s);
-  if (a.S > 8) return gauss_go<16, WT>(a, p, s);
-  if (a.S > 4) return gauss_go<8, WT>(a, p, s);
-  if (a.S > 2) return gauss_go<4, WT>(a, p, s);
-  if (a.S > 1) return gauss_go<2, WT>(a, p, s);
-  return gauss_go<1, WT>(a, p, s);
+template <bool WT, bool MEM>
+int gauss_width(const GaussArgs& a, const GaussPlan& p, int64_t M, hipStream_t s) {
+  if (a.S > 16) return gauss_go<32, WT, MEM>(a, p, M, s);
+  if (a.S > 8) return gauss_go<16, WT, MEM>(a, p, M, s);
+  if (a.S > 4) return gauss_go<8, WT, MEM>(a, p, M, s);
+  if (a.S > 2) return gauss_go<4, WT, MEM>(a, p, M, s);
+  if (a.S > 1) return gauss_go<2, WT, MEM>(a, p, M, s);
+  return gauss_go<1, WT, MEM>(a, p, M, s);
 }
 
 // the decode and filter kernels' view of this file's emissions (hmm_gauss_decode_dev.h): the table is
@@ -754,16 +784,34 @@ int launch_hmm_gauss_estep(const float* log_pi, const float* log_A, const float*
                            int64_t B, int64_t T, int64_t S, int64_t D, double* pi_cnt, double* trans_cnt,
                            double* occ, double* m1, double* m2, float* loglik, float* gamma, void* ws,
                            hipStream_t s) {
-  if (!hmm_gauss_supported(S, D) || !gauss_sizes_ok(B, T)) return VQHMM_EUNSUPPORTED;
+  return launch_hmm_gauss_estep_batched(log_pi, log_A, mean, log_var, x, lengths, shift, weights, B, T, S, D, 1,
+                                        pi_cnt, trans_cnt, occ, m1, m2, loglik, gamma, ws, s);
+}
+
+// M members: M single-model workspaces, each rounded up to 256 bytes
+size_t hmm_gauss_estep_batched_ws_bytes(int64_t B, int64_t T, int64_t S, int64_t D, int64_t M) {
+  if (!hmm_gauss_supported(S, D) || !hmm_code_members_supported(M) || B < 0 || T < 0 || !gauss_sizes_ok(B, T))
+    return 0;
+  return (size_t)M * r256(gauss_plan(B, T, S, D).bytes);
+}
+
+int launch_hmm_gauss_estep_batched(const float* log_pi, const float* log_A, const float* mean, const float* log_var,
+                                   const float* x, const int64_t* lengths, const float* shift, const float* weights,
+                                   int64_t B, int64_t T, int64_t S, int64_t D, int64_t M, double* pi_cnt,
+                                   double* trans_cnt, double* occ, double* m1, double* m2, float* loglik,
+                                   float* gamma, void* ws, hipStream_t s) {
+  if (!hmm_gauss_supported(S, D) || !hmm_code_members_supported(M) || !gauss_sizes_ok(B, T))
+    return VQHMM_EUNSUPPORTED;
   if (B == 0 || T == 0) {
-    if (hipMemsetAsync(pi_cnt, 0, sizeof(double) * S, s) != hipSuccess ||
-        hipMemsetAsync(trans_cnt, 0, sizeof(double) * S * S, s) != hipSuccess ||
-        hipMemsetAsync(occ, 0, sizeof(double) * S, s) != hipSuccess ||
-        hipMemsetAsync(m1, 0, sizeof(double) * S * D, s) != hipSuccess ||
-        hipMemsetAsync(m2, 0, sizeof(double) * S * D, s) != hipSuccess)
+    if (hipMemsetAsync(pi_cnt, 0, sizeof(double) * M * S, s) != hipSuccess ||
+        hipMemsetAsync(trans_cnt, 0, sizeof(double) * M * S * S, s) != hipSuccess ||
+        hipMemsetAsync(occ, 0, sizeof(double) * M * S, s) != hipSuccess ||
+        hipMemsetAsync(m1, 0, sizeof(double) * M * S * D, s) != hipSuccess ||
+        hipMemsetAsync(m2, 0, sizeof(double) * M * S * D, s) != hipSuccess)
       return VQHMM_ELAUNCH;
     // length-0 sequences: loglik = NaN (all-ones words)
-    if (B > 0 && loglik && hipMemsetAsync(loglik, 0xFF, sizeof(float) * B, s) != hipSuccess) return VQHMM_ELAUNCH;
+    if (B > 0 && loglik && hipMemsetAsync(loglik, 0xFF, sizeof(float) * M * B, s) != hipSuccess)
+      return VQHMM_ELAUNCH;
     return VQHMM_OK;
   }
   const GaussPlan p = gauss_plan(B, T, S, D);
@@ -775,11 +823,13 @@ int launch_hmm_gauss_estep(const float* log_pi, const float* log_A, const float*
   a.alpha = reinterpret_cast<float*>(w);
   a.part = reinterpret_cast<double*>(w + p.off_part);
   a.loglik = loglik; a.gamma = gamma;
-  const int rc = weights ? gauss_width<true>(a, p, s) : gauss_width<false>(a, p, s);
+  a.mstride = r256(p.bytes);
+  const int rc = weights ? (M > 1 ? gauss_width<true, true>(a, p, M, s) : gauss_width<true, false>(a, p, M, s))
+                         : (M > 1 ? gauss_width<false, true>(a, p, M, s) : gauss_width<false, false>(a, p, M, s));
   if (rc) return rc;
   const int64_t NE = 2 * S * D + S * S + 2 * S;
-  gauss_reduce_kernel<<<(unsigned)cdiv(NE, GE_RK), GE_RK * GE_RP, 0, s>>>(a.part, (int)p.nblk, (int)S, (int)D,
-                                                                         pi_cnt, trans_cnt, occ, m1, m2);
+  gauss_reduce_kernel<<<dim3((unsigned)cdiv(NE, GE_RK), (unsigned)M), GE_RK * GE_RP, 0, s>>>(
+      a.part, a.mstride, (int)p.nblk, (int)S, (int)D, pi_cnt, trans_cnt, occ, m1, m2);
   VQHMM_LAUNCH_CHECK();
   return VQHMM_OK;
 }

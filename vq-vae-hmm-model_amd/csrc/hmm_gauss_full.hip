@@ -30,6 +30,11 @@
 // gamma inside their length (plain stores of 1 into a zeroed array), then one wave per (sequence, 64-step chunk)
 // stages x and gamma, adds the chunk's products to its slab, and the same reduce launch finishes.
 //
+// Members.  As in hmm_gauss.hip: blockIdx.y of the E-step and of the reduce kernel is the member of a stack of M
+// models that share x, lengths and shift (the batched entry; the single-model entry is M = 1).  A member has its own
+// parameter slices, weights row, alpha rows, partials (`mstride` workspace bytes apart) and output blocks and runs
+// the single model's plan, so its bits are the single-model call's.  The moments entry has no member axis.
+//
 // Addressing.  x and gamma are read only at rows t < L of the wave's own sequence, parameters only at (s, i, j <=
 // i), the workspace only inside the sequence's own rows.
 //
@@ -214,14 +219,29 @@ struct GaussFullArgs {
   const float* x;
   const int64_t* lengths;
   const float* shift;    // (D), nullable (= 0)
-  const float* weights;  // (B), nullable (= all 1)
+  const float* weights;  // (M, B), nullable (= all 1)
   int64_t B;
   int T, S, D;
   float* alpha;   // (B, T, S) scaled forward vectors
   double* part;   // [gridDim.x][m1 S*D | m2 S*P | trans S*S | pi S | occ S]
   float* loglik;  // nullable
   float* gamma;   // nullable
+  size_t mstride;  // bytes from a member's alpha / part to the next member's
 };
+
+// member m's view of the arguments (m = 0 changes nothing): x, lengths and shift are shared
+__device__ __forceinline__ GaussFullArgs gauss_full_member(GaussFullArgs a, int64_t m) {
+  a.log_pi += m * a.S;
+  a.log_A += m * a.S * a.S;
+  a.mean += m * a.S * a.D;
+  a.prec += m * a.S * a.D * a.D;
+  if (a.weights) a.weights += m * a.B;
+  a.alpha = reinterpret_cast<float*>(reinterpret_cast<char*>(a.alpha) + m * a.mstride);
+  a.part = reinterpret_cast<double*>(reinterpret_cast<char*>(a.part) + m * a.mstride);
+  if (a.loglik) a.loglik += m * a.B;
+  if (a.gamma) a.gamma += m * a.B * (int64_t)a.T * a.S;
+  return a;
+}
 
 // ------------------------------------------------------------------------------ emission entry
 // one chunk of 64 rows per wave; LDS: [W S*P][mu S*D][c S] [per wave: xbuf 64*DS, obuf 64*OS]
@@ -275,10 +295,11 @@ __global__ __launch_bounds__(256) void gauss_full_emission_kernel(const float* _
 // out = sum over the partials in a fixed order (gauss_reduce_kernel's scheme): 16 elements per workgroup, thread
 // (py, kx) adds partials py, py + 16, .. of element kx in index order, then the 16 sums are added in py order.  An
 // m2 sum is written to both triangles.  pi_cnt == nullptr (the moments entry): trans and pi are neither read nor
-// written
+// written.  blockIdx.y is the member: its own partials (mstride bytes apart) and output blocks
 constexpr int GF_RK = 16, GF_RP = 16;
-__global__ __launch_bounds__(GF_RK* GF_RP) void gauss_full_reduce_kernel(const double* __restrict__ part, int np,
-                                                                         int S, int D, double* __restrict__ pi_cnt,
+__global__ __launch_bounds__(GF_RK* GF_RP) void gauss_full_reduce_kernel(const double* __restrict__ part,
+                                                                         size_t mstride, int np, int S, int D,
+                                                                         double* __restrict__ pi_cnt,
                                                                          double* __restrict__ trans_cnt,
                                                                          double* __restrict__ occ,
                                                                          double* __restrict__ m1,
@@ -287,6 +308,15 @@ __global__ __launch_bounds__(GF_RK* GF_RP) void gauss_full_reduce_kernel(const d
   const int P = gf_tri(D), SD = S * D, SP2 = S * P, SS = S * S, NE = SD + SP2 + SS + 2 * S;
   const int kx = threadIdx.x % GF_RK, py = threadIdx.x / GF_RK;
   const int k = (int)blockIdx.x * GF_RK + kx;
+  const int64_t mem = blockIdx.y;
+  part = reinterpret_cast<const double*>(reinterpret_cast<const char*>(part) + mem * mstride);
+  if (pi_cnt != nullptr) {
+    pi_cnt += mem * S;
+    trans_cnt += mem * SS;
+  }
+  occ += mem * S;
+  m1 += mem * SD;
+  m2 += mem * (int64_t)SD * D;
   const bool chain_cnt = k >= SD + SP2 && k < SD + SP2 + SS + S;
   const bool live = k < NE && !(chain_cnt && pi_cnt == nullptr);
   double acc = 0.0;
@@ -319,10 +349,12 @@ __global__ __launch_bounds__(GF_RK* GF_RP) void gauss_full_reduce_kernel(const d
 }
 
 // -------------------------------------------------------------------------------------- E-step
-// all-ones weights give the bits of weights = NULL: fma(1.0, v, acc) is the plain fp64 add
-template <int SP>
-__global__ __launch_bounds__(256) void gauss_full_estep_kernel(const GaussFullArgs a) {
+// all-ones weights give the bits of weights = NULL: fma(1.0, v, acc) is the plain fp64 add.  MEM: the launch has
+// more than one member (blockIdx.y); with one the arguments stay kernel arguments, as in hmm_code.hip
+template <int SP, bool MEM>
+__global__ __launch_bounds__(256) void gauss_full_estep_kernel(const GaussFullArgs a0) {
   extern __shared__ double gf_smem[];
+  const GaussFullArgs a = MEM ? gauss_full_member(a0, blockIdx.y) : a0;
   constexpr int ES = SP | 1;  // row stride of the chunk's emission buffer (odd: the lane = time pass is conflict-free)
   const int S = a.S, D = a.D, T = a.T;
   const int P = gf_tri(D), SD = S * D, SL = SD + S * P, NT = S * S + 2 * S, DS = gf_odd(D);
@@ -778,25 +810,26 @@ GaussFullPlan gauss_moments_plan(int64_t B, int64_t T, int64_t S, int64_t D) {
   return gf_plan(sh, pw, B * cdiv(T, CE_CH), (size_t)B * 4, S, D);
 }
 
-template <int SP>
-int gauss_full_go(const GaussFullArgs& a, const GaussFullPlan& p, hipStream_t s) {
-  auto kern = gauss_full_estep_kernel<SP>;
+template <int SP, bool MEM>
+int gauss_full_go(const GaussFullArgs& a, const GaussFullPlan& p, int64_t M, hipStream_t s) {
+  auto kern = gauss_full_estep_kernel<SP, MEM>;
   // more than 64 KB of dynamic LDS has to be asked for, once per kernel
   static const hipError_t big_lds = hipFuncSetAttribute(
       reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)GF_LDS_MAX);
   (void)big_lds;
-  kern<<<(unsigned)p.nblk, 64 * p.nw, p.lds_bytes, s>>>(a);
+  kern<<<dim3((unsigned)p.nblk, (unsigned)M), 64 * p.nw, p.lds_bytes, s>>>(a);
   VQHMM_LAUNCH_CHECK();
   return VQHMM_OK;
 }
 
-int gauss_full_width(const GaussFullArgs& a, const GaussFullPlan& p, hipStream_t s) {
-  if (a.S > 16) return gauss_full_go<32>(a, p, s);
-  if (a.S > 8) return gauss_full_go<16>(a, p, s);
-  if (a.S > 4) return gauss_full_go<8>(a, p, s);
-  if (a.S > 2) return gauss_full_go<4>(a, p, s);
-  if (a.S > 1) return gauss_full_go<2>(a, p, s);
-  return gauss_full_go<1>(a, p, s);
+template <bool MEM>
+int gauss_full_width(const GaussFullArgs& a, const GaussFullPlan& p, int64_t M, hipStream_t s) {
+  if (a.S > 16) return gauss_full_go<32, MEM>(a, p, M, s);
+  if (a.S > 8) return gauss_full_go<16, MEM>(a, p, M, s);
+  if (a.S > 4) return gauss_full_go<8, MEM>(a, p, M, s);
+  if (a.S > 2) return gauss_full_go<4, MEM>(a, p, M, s);
+  if (a.S > 1) return gauss_full_go<2, MEM>(a, p, M, s);
+  return gauss_full_go<1, MEM>(a, p, M, s);
 }
 
 // the batch sizes the launches index (and whose workspace size fits size_t): the queries and the launchers agree
@@ -872,16 +905,36 @@ int launch_hmm_gauss_full_estep(const float* log_pi, const float* log_A, const f
                                 int64_t B, int64_t T, int64_t S, int64_t D, double* pi_cnt, double* trans_cnt,
                                 double* occ, double* m1, double* m2, float* loglik, float* gamma, void* ws,
                                 hipStream_t s) {
-  if (!hmm_gauss_full_supported(S, D) || !gauss_full_sizes_ok(B, T)) return VQHMM_EUNSUPPORTED;
+  return launch_hmm_gauss_full_estep_batched(log_pi, log_A, mean, prec_chol, x, lengths, shift, weights, B, T, S, D,
+                                             1, pi_cnt, trans_cnt, occ, m1, m2, loglik, gamma, ws, s);
+}
+
+// M members: M single-model workspaces, each rounded up to 256 bytes
+size_t hmm_gauss_full_estep_batched_ws_bytes(int64_t B, int64_t T, int64_t S, int64_t D, int64_t M) {
+  if (!hmm_gauss_full_supported(S, D) || !hmm_code_members_supported(M) || B < 0 || T < 0 ||
+      !gauss_full_sizes_ok(B, T))
+    return 0;
+  return (size_t)M * r256(gauss_full_plan(B, T, S, D).bytes);
+}
+
+int launch_hmm_gauss_full_estep_batched(const float* log_pi, const float* log_A, const float* mean,
+                                        const float* prec_chol, const float* x, const int64_t* lengths,
+                                        const float* shift, const float* weights, int64_t B, int64_t T, int64_t S,
+                                        int64_t D, int64_t M, double* pi_cnt, double* trans_cnt, double* occ,
+                                        double* m1, double* m2, float* loglik, float* gamma, void* ws,
+                                        hipStream_t s) {
+  if (!hmm_gauss_full_supported(S, D) || !hmm_code_members_supported(M) || !gauss_full_sizes_ok(B, T))
+    return VQHMM_EUNSUPPORTED;
   if (B == 0 || T == 0) {
-    if (hipMemsetAsync(pi_cnt, 0, sizeof(double) * S, s) != hipSuccess ||
-        hipMemsetAsync(trans_cnt, 0, sizeof(double) * S * S, s) != hipSuccess ||
-        hipMemsetAsync(occ, 0, sizeof(double) * S, s) != hipSuccess ||
-        hipMemsetAsync(m1, 0, sizeof(double) * S * D, s) != hipSuccess ||
-        hipMemsetAsync(m2, 0, sizeof(double) * S * D * D, s) != hipSuccess)
+    if (hipMemsetAsync(pi_cnt, 0, sizeof(double) * M * S, s) != hipSuccess ||
+        hipMemsetAsync(trans_cnt, 0, sizeof(double) * M * S * S, s) != hipSuccess ||
+        hipMemsetAsync(occ, 0, sizeof(double) * M * S, s) != hipSuccess ||
+        hipMemsetAsync(m1, 0, sizeof(double) * M * S * D, s) != hipSuccess ||
+        hipMemsetAsync(m2, 0, sizeof(double) * M * S * D * D, s) != hipSuccess)
       return VQHMM_ELAUNCH;
     // length-0 sequences: loglik = NaN (all-ones words)
-    if (B > 0 && loglik && hipMemsetAsync(loglik, 0xFF, sizeof(float) * B, s) != hipSuccess) return VQHMM_ELAUNCH;
+    if (B > 0 && loglik && hipMemsetAsync(loglik, 0xFF, sizeof(float) * M * B, s) != hipSuccess)
+      return VQHMM_ELAUNCH;
     return VQHMM_OK;
   }
   const GaussFullPlan p = gauss_full_plan(B, T, S, D);
@@ -893,11 +946,12 @@ int launch_hmm_gauss_full_estep(const float* log_pi, const float* log_A, const f
   a.alpha = reinterpret_cast<float*>(w);
   a.part = reinterpret_cast<double*>(w + p.off_part);
   a.loglik = loglik; a.gamma = gamma;
-  const int rc = gauss_full_width(a, p, s);
+  a.mstride = r256(p.bytes);
+  const int rc = M > 1 ? gauss_full_width<true>(a, p, M, s) : gauss_full_width<false>(a, p, M, s);
   if (rc) return rc;
   const int64_t NE = S * D + S * gf_tri((int)D) + S * S + 2 * S;
-  gauss_full_reduce_kernel<<<(unsigned)cdiv(NE, GF_RK), GF_RK * GF_RP, 0, s>>>(a.part, (int)p.nblk, (int)S, (int)D,
-                                                                              pi_cnt, trans_cnt, occ, m1, m2);
+  gauss_full_reduce_kernel<<<dim3((unsigned)cdiv(NE, GF_RK), (unsigned)M), GF_RK * GF_RP, 0, s>>>(
+      a.part, a.mstride, (int)p.nblk, (int)S, (int)D, pi_cnt, trans_cnt, occ, m1, m2);
   VQHMM_LAUNCH_CHECK();
   return VQHMM_OK;
 }
@@ -932,8 +986,8 @@ int launch_hmm_gauss_moments(const float* x, const float* gamma, const int64_t* 
   gauss_moments_kernel<<<(unsigned)p.nblk, 64 * p.nw, p.lds_bytes, s>>>(a);
   VQHMM_LAUNCH_CHECK();
   const int64_t NE = S * D + S * gf_tri((int)D) + S * S + 2 * S;
-  gauss_full_reduce_kernel<<<(unsigned)cdiv(NE, GF_RK), GF_RK * GF_RP, 0, s>>>(a.part, (int)p.nblk, (int)S, (int)D,
-                                                                              nullptr, nullptr, occ, m1, m2);
+  gauss_full_reduce_kernel<<<(unsigned)cdiv(NE, GF_RK), GF_RK * GF_RP, 0, s>>>(a.part, 0, (int)p.nblk, (int)S,
+                                                                              (int)D, nullptr, nullptr, occ, m1, m2);
   VQHMM_LAUNCH_CHECK();
   return VQHMM_OK;
 }

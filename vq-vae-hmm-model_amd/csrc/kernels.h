@@ -547,6 +547,14 @@ int launch_hmm_gauss_estep(const float* log_pi, const float* log_A, const float*
                            int64_t B, int64_t T, int64_t S, int64_t D, double* pi_cnt, double* trans_cnt,
                            double* occ, double* m1, double* m2, float* loglik, float* gamma, void* ws,
                            hipStream_t s);
+// ... for M stacked models on the shared (x, lengths, shift): parameters and outputs (M, ...), weights (M,B);
+// 1 <= M <= 65535 (hmm_code_members_supported), the single-model entry is M = 1
+size_t hmm_gauss_estep_batched_ws_bytes(int64_t B, int64_t T, int64_t S, int64_t D, int64_t M);
+int launch_hmm_gauss_estep_batched(const float* log_pi, const float* log_A, const float* mean, const float* log_var,
+                                   const float* x, const int64_t* lengths, const float* shift, const float* weights,
+                                   int64_t B, int64_t T, int64_t S, int64_t D, int64_t M, double* pi_cnt,
+                                   double* trans_cnt, double* occ, double* m1, double* m2, float* loglik,
+                                   float* gamma, void* ws, hipStream_t s);
 int launch_hmm_gauss_sample(const float* log_pi, const float* log_A, const float* mean, const float* log_var,
                             const float* uniforms, const float* normals, int64_t N, int64_t T, int64_t S,
                             int64_t D, int32_t* states, float* x, hipStream_t s);
@@ -563,6 +571,13 @@ int launch_hmm_gauss_full_estep(const float* log_pi, const float* log_A, const f
                                 int64_t B, int64_t T, int64_t S, int64_t D, double* pi_cnt, double* trans_cnt,
                                 double* occ, double* m1, double* m2, float* loglik, float* gamma, void* ws,
                                 hipStream_t s);
+size_t hmm_gauss_full_estep_batched_ws_bytes(int64_t B, int64_t T, int64_t S, int64_t D, int64_t M);
+int launch_hmm_gauss_full_estep_batched(const float* log_pi, const float* log_A, const float* mean,
+                                        const float* prec_chol, const float* x, const int64_t* lengths,
+                                        const float* shift, const float* weights, int64_t B, int64_t T, int64_t S,
+                                        int64_t D, int64_t M, double* pi_cnt, double* trans_cnt, double* occ,
+                                        double* m1, double* m2, float* loglik, float* gamma, void* ws,
+                                        hipStream_t s);
 int launch_hmm_gauss_moments(const float* x, const float* gamma, const int64_t* lengths, const float* shift,
                              const float* weights, int64_t B, int64_t T, int64_t S, int64_t D, double* occ,
                              double* m1, double* m2, void* ws, hipStream_t s);

@@ -69,6 +69,10 @@ _SIGS = {
     "vqhmm_gauss_estep_workspace_size": (c_sz, [c_i64, c_i64, c_i64, c_i64]),
     "vqhmm_gauss_estep_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64,
                                              c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "vqhmm_gauss_estep_batched_workspace_size": (c_sz, [c_i64, c_i64, c_i64, c_i64, c_i64]),
+    "vqhmm_gauss_estep_batched_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64,
+                                                     c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                                     c_vp, c_sz, c_vp]),
     "vqhmm_gauss_sample_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp,
                                               c_vp, c_vp]),
     "vqhmm_gauss_full_emission_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp,
@@ -77,6 +81,10 @@ _SIGS = {
     "vqhmm_gauss_full_estep_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64,
                                                   c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz,
                                                   c_vp]),
+    "vqhmm_gauss_full_estep_batched_workspace_size": (c_sz, [c_i64, c_i64, c_i64, c_i64, c_i64]),
+    "vqhmm_gauss_full_estep_batched_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64,
+                                                          c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                                          c_vp, c_vp, c_vp, c_sz, c_vp]),
     "vqhmm_gauss_moments_workspace_size": (c_sz, [c_i64, c_i64, c_i64, c_i64]),
     "vqhmm_gauss_moments_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp,
                                                c_vp, c_vp, c_sz, c_vp]),

@@ -15,6 +15,9 @@ same moments under a caller-supplied posterior (vqhmm_gauss_moments_f32).
 Read-outs of a fitted model, both covariance types, fused on x (no emission table, no expanded log_A): `decode`
 (the MAP regime path, vqhmm_gauss_viterbi_f32 / vqhmm_gauss_full_viterbi_f32), `filter` / `update` (the causal
 filter with a carried (B,S) state, vqhmm_gauss_filter_f32 / vqhmm_gauss_full_filter_f32) and `predict_next`.
+
+Restarts (`fit(n_init=R)`) run on gauss_hmm_ensemble.GaussianHMMEnsemble, R models in one launch
+(vqhmm_gauss_estep_batched_f32 / vqhmm_gauss_full_estep_batched_f32).
 """
 import torch
 
@@ -185,6 +188,45 @@ def _estep_full(what, log_pi, log_A, mean, prec, x, lengths, shift, weights, wan
     if want_gamma:
         out["gamma"] = gamma
     return out
+
+
+def _estep_members(what, full, log_pi, log_A, mean, last, x, lengths, shift, weights, want_loglik, want_gamma,
+                   max_workspace_bytes=None):
+    """vqhmm_gauss_estep_batched_f32 / vqhmm_gauss_full_estep_batched_f32 on stacked contiguous fp32 parameters
+    (M,S) / (M,S,S) / (M,S,D) / `last` = log_var (M,S,D) or W (M,S,D,D), the shared x (B,T,D), lengths (B), shift (D)
+    or None and weights (M,B) fp32 or None -> (pi_cnt (M,S), trans_cnt (M,S,S), occ (M,S), m1 (M,S,D), m2 (M,S,D) or
+    (M,S,D,D) fp64, loglik (M,B) or None, gamma (M,B,T,S) or None).  The members run in groups whose workspace fits
+    max_workspace_bytes (None: one group); a member's bits do not depend on its group."""
+    M, S, D = mean.shape
+    B, T = x.shape[:2]
+    dev = x.device
+    f64 = dict(dtype=torch.float64, device=dev)
+    pi, tr, occ = torch.empty((M, S), **f64), torch.empty((M, S, S), **f64), torch.empty((M, S), **f64)
+    m1 = torch.empty((M, S, D), **f64)
+    m2 = torch.empty((M, S, D, D) if full else (M, S, D), **f64)
+    ll = torch.empty((M, B), dtype=torch.float32, device=dev) if want_loglik else None
+    gm = torch.empty((M, B, T, S), dtype=torch.float32, device=dev) if want_gamma else None
+    lib = _ext.load()
+    size, entry = ((lib.vqhmm_gauss_full_estep_batched_workspace_size, lib.vqhmm_gauss_full_estep_batched_f32) if full
+                   else (lib.vqhmm_gauss_estep_batched_workspace_size, lib.vqhmm_gauss_estep_batched_f32))
+    G = min(M, 65535)
+    if max_workspace_bytes is not None:
+        per = size(B, T, S, D, 1)
+        G = max(1, min(G, int(max_workspace_bytes) // max(per, 1)))
+    nb = size(B, T, S, D, G)
+    ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=dev)
+    st = _ext.stream_ptr(dev)
+
+    def at(t, m0):
+        return _ext.ptr(t[m0:]) if t is not None else _ext.ptr(None)
+
+    with torch.no_grad():
+        for m0 in range(0, M, G):
+            _ext.check(entry(
+                at(log_pi, m0), at(log_A, m0), at(mean, m0), at(last, m0), _ext.ptr(x), _ext.ptr(lengths),
+                _ext.ptr(shift), at(weights, m0), B, T, S, D, min(G, M - m0), at(pi, m0), at(tr, m0), at(occ, m0),
+                at(m1, m0), at(m2, m0), at(ll, m0), at(gm, m0), _ext.ptr(ws), nb, st), what)
+    return pi, tr, occ, m1, m2, ll, gm
 
 
 class _GaussFullLogProb(torch.autograd.Function):
@@ -584,21 +626,76 @@ class GaussianHMM(torch.nn.Module):
         else:
             self.log_var.copy_(torch.log(var).float().expand(S, D))
 
+    @torch.no_grad()
+    def _restart_ensemble(self, n_init, x, lengths, generator=None):
+        """The starts of fit(n_init=R): member 0 = the current parameters; members 1..R-1 = pi and A as
+        GaussianHMM(S, D, covariance_type, generator) draws them, in that order, with this model's structural zeros
+        imposed and the rows renormalised (a mixture's rows of A tied to its pi), means at S distinct counted
+        positions of x (Codebook's draw with `generator`) and one shared per-dimension variance, the data's."""
+        from .gauss_hmm_ensemble import GaussianHMMEnsemble
+        S, D = self.num_states, self.dim
+        dev = x.device
+        T = x.shape[1]
+        mask = (torch.arange(T, device=dev).unsqueeze(0) < lengths.clamp(0, T).unsqueeze(1)).unsqueeze(2)
+        n = mask.sum().clamp_min(1)
+        xd = x.double()
+        mu = torch.where(mask, xd, 0.0).sum((0, 1)) / n
+        var = (torch.where(mask, (xd - mu) ** 2, 0.0).sum((0, 1)) / n).clamp_min(1e-6)
+        z = x.transpose(1, 2).contiguous()
+        starts = [self]
+        for _ in range(int(n_init) - 1):
+            h = GaussianHMM(S, D, self.covariance_type, generator=generator).to(dev)
+            h.mixture = self.mixture
+            for k in ("log_pi", "log_A"):
+                new = torch.where(getattr(self, k) != float("-inf"), getattr(h, k).double(), float("-inf"))
+                lse = torch.logsumexp(new, -1, keepdim=True)
+                getattr(h, k).copy_(torch.where(lse != float("-inf"), new - lse, new).float())
+            if self.mixture:
+                h.log_A.copy_(h.log_pi.unsqueeze(0).expand_as(h.log_A))
+            h.mean.copy_(Codebook(S, D).to(dev)._pick(z, lengths, S, generator))
+            if self.full:
+                h.scale_tril.copy_(torch.diag(torch.sqrt(var)).float().expand(S, D, D))
+            else:
+                h.log_var.copy_(torch.log(var).float().expand(S, D))
+            starts.append(h)
+        return GaussianHMMEnsemble.from_models(starts)
+
     def fit(self, x, lengths=None, n_iter=20, tol=None, prior_count=0.0, var_floor=None, init="kmeans",
-            mixture=False, generator=None, reg_covar=None):
+            mixture=False, generator=None, reg_covar=None, n_init=1):
         """Baum-Welch: alternate e_step and m_step.  Returns the total log-likelihoods, one per iteration, each
         under the parameters before that iteration's M-step (0-dim device tensors with tol=None, so the loop has
         no host sync; floats with tol, which stops once the improvement per observed position is < tol).
         init="kmeans" first runs init_kmeans, init=None starts from the current parameters.  The moments are
         taken about the data mean (computed once).  mixture=True fits the Gaussian mixture (as_mixture).
-        var_floor ("diag") and reg_covar ("full") are m_step's, 1e-6 by default."""
+        var_floor ("diag") and reg_covar ("full") are m_step's, 1e-6 by default.
+
+        n_init = R > 1: R chains in one batched E-step per iteration (GaussianHMMEnsemble): member 0 starts where
+        the plain fit would (after init_kmeans, or from the current parameters with init=None), members 1..R-1
+        from the random starts of _restart_ensemble, drawn from `generator`.  The member with the largest total
+        log-likelihood under its final parameters (one more batched E-step) is copied into this model, selected
+        on the device; the history returned is that member's.  No host sync; `tol` cannot be combined with it."""
         if init not in ("kmeans", None):
             raise ValueError("GaussianHMM.fit: init is 'kmeans' or None")
+        n_init = int(n_init)
+        if n_init < 1:
+            raise ValueError("GaussianHMM.fit: n_init >= 1")
+        if n_init > 1 and tol is not None:
+            raise ValueError("GaussianHMM.fit: tol needs a host sync per iteration and cannot be combined with "
+                             "n_init > 1")
         x, lengths, B, T = self._inputs(x, lengths)
         if mixture:
             self.as_mixture()
         if init == "kmeans":
             self.init_kmeans(x, lengths, generator=generator)
+        if n_init > 1:
+            ens = self._restart_ensemble(n_init, x, lengths, generator)
+            hist = ens.fit(x, lengths, n_iter=n_iter, prior_count=prior_count, var_floor=var_floor,
+                           reg_covar=reg_covar)
+            best = ens.best_index(x, lengths)
+            with torch.no_grad():
+                for k in ("log_pi", "log_A", "mean", "scale_tril" if self.full else "log_var"):
+                    getattr(self, k).copy_(getattr(ens, k).index_select(0, best)[0])
+            return list(hist.index_select(1, best)[:, 0].unbind(0))
         mask = (torch.arange(T, device=x.device).unsqueeze(0) < lengths.clamp(0, T).unsqueeze(1)).unsqueeze(2)
         npos_t = mask.sum().clamp_min(1)
         shift = (torch.where(mask, x.double(), 0.0).sum((0, 1)) / npos_t).float().contiguous()
