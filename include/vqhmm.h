@@ -578,6 +578,59 @@ int vqhmm_gauss_full_filter_f32(const float* log_pi, const float* log_A,
                                 int64_t B, int64_t T, int64_t S, int64_t D,
                                 float* filt, float* last, float* loglik, void* stream);
 
+/* ------------------- Gaussian HMM scenarios: Monte Carlo paths with on-chip RNG ----
+ * vqhmm_gauss_scenario_f32 (hmm_gauss_scenario.hip): from a regime distribution per start to N simulated
+ * paths of H steps per start, in one launch: the regime chain, the Gaussian returns and a portfolio's
+ * wealth path, with every random number generated on chip.  start (B,S) fp32: non-negative weights of
+ * the regime at simulated step 0 (need not be normalised).  log_A (S,S), mean (S,D) as above.  scale:
+ * full = 0: (S,D) standard deviations; full = 1: (S,D,D) row-major lower Cholesky factors L (Sigma = L
+ * L^T), of which only the lower triangle is read.  1 <= S <= 32; D <= 64 (full = 0); D <= 32 and S*D*D <=
+ * 8192 (full = 1); H <= 2^28, B*N <= 2^36, B*N*H <= 2^48 (else VQHMM_EUNSUPPORTED).  port (S,D) fp32,
+ * nullable: the holdings taken when a rebalance finds the path in that regime.  Path (b, n) is path
+ * (b0 + b, n0 + n) of the seed's stream: a call on a sub-range of starts or paths returns the bits of the
+ * full call's rows.
+ *
+ * Outputs, each nullable, at least one not: states (B,N,H) int32, x (B,N,H,D) fp32, wealth (B,N,H) fp32,
+ * final_wealth (B,N) fp32, drawdown (B,N) fp32.  wealth, final_wealth and drawdown need port.  What is
+ * written does not depend on which other outputs are asked for.
+ *
+ * Random numbers: Philox4x32-10 (Random123: multipliers 0xD2511F53, 0xCD9E8D57, key increments 0x9E3779B9,
+ * 0xBB67AE85), key = (seed & 0xffffffff, seed >> 32), counter = (n0 + n, b0 + b, t, j).  Block j = 0: its
+ * word 0, w, gives the regime uniform u = (w >> 8) * 2^-24.  Block j = 1 + d / 4 (integer division) gives
+ * the normals of dimensions 4 (j - 1) .. 4 (j - 1) + 3 by Box-Muller on the word pairs (0,1) and (2,3):
+ * u1 = ((wa >> 8) + 1) * 2^-24, u2 = (wb >> 8) * 2^-24, r = sqrtf(-2 logf(u1)), eps = r cospif(2 u2) for
+ * the even and r sinpif(2 u2) for the odd dimension.  u1 >= 2^-24, so the tails are cut at |eps| <= sqrt(48
+ * ln 2) = 5.77 (mass 8e-9 per draw).
+ *
+ * Chain: z_0 is drawn from p_k = start[b,k], z_t from p_k = expf(log_A[z_{t-1}, k]), by
+ * vqhmm_code_sample_f32's rule: the first k with p_k > 0 and u < run_k / total (run the fp32 running sum
+ * in index order, total its last value), else the last k with p_k > 0; a zero weight is never drawn.  A
+ * negative or non-finite entry of start[b], or a total (of start[b], or of the row entered) that is 0 or
+ * not finite, fails the path from that step on: states = -1 and x = wealth = NaN from there, final_wealth
+ * = drawdown = NaN; the other paths are untouched.
+ *
+ * Returns: full = 0: x[d] = fmaf(scale[z,d], eps_d, mean[z,d]); full = 1: x[i] = the fp32 fma chain acc =
+ * mean[z,i], acc = fmaf(L[z,i,j], eps_j, acc) for j = 0..i in index order.
+ *
+ * Wealth, carried in fp64: w = 1, peak = 1, dd = 0, nothing held.  At t % rebalance == 0: w -= w * tx_cost *
+ * sum_d |port[z_t,d] - held_d| (the sum in fp64 in index order), then held = port[z_t].  Every step: w *=
+ * 1 + sum_d held_d x[t,d] (fp64, index order, on the fp32 x); wealth[b,n,t] = (float) w; peak = max(peak,
+ * w); dd = max(dd, 1 - w / peak).  final_wealth = (float) w after the last step (the bits of wealth[b,n,
+ * H-1]), drawdown = (float) dd.
+ *
+ * No workspace, no host sync, deterministic, graph-capturable, 64-bit offsets, every global access inside
+ * its own array.  Return codes, checked in this order on the host before any launch: a negative size (B,
+ * N, H, S, D, b0, n0) -> VQHMM_EINVAL; S, D or the sizes out of range -> VQHMM_EUNSUPPORTED; B*N*H == 0
+ * -> VQHMM_OK without a launch; a null required pointer (start, log_A, mean, scale; port with a wealth
+ * output; every output NULL), rebalance < 1, or b0 + B or n0 + N above 2^32 -> VQHMM_EINVAL. */
+int vqhmm_gauss_scenario_f32(const float* start, const float* log_A, const float* mean,
+                             const float* scale, int full, const float* port,
+                             int64_t rebalance, float tx_cost, uint64_t seed,
+                             int64_t b0, int64_t n0,
+                             int64_t B, int64_t N, int64_t H, int64_t S, int64_t D,
+                             int32_t* states, float* x, float* wealth,
+                             float* final_wealth, float* drawdown, void* stream);
+
 /* -------------------------------------------------- codebook learning ----
  * Per-code statistics of a batch under given assignments, the quantizer's backward from the same
  * pass, and the channels-first lookup (pseudocode.txt:8-32, the codebook's side; vq_codebook.hip).

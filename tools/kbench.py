@@ -41,6 +41,11 @@
                                                          full covariances; --old-route: also the emission entry +
                                                          expanded log_A + viterbi / forward_filter; the filter leg
                                                          also times the E-step of the same shape)
+    python tools/kbench.py gauss_scenario --B 512 --N 256 --T 64 --K 3 --D 12 [--full] [--old-route]
+                                                        (GaussianHMM.simulate: B starts x N paths x T steps, final +
+                                                         drawdown only and with x written; --old-route: also
+                                                         simulate_paths + torch.randn + gather / matmul + torch wealth,
+                                                         five alternating pairs, a check line on the distributions)
     python tools/kbench.py vq_stats --B 2048 --Dv 64 --T 200 --K 32 [--old-route]
     python tools/kbench.py vq_bwd --B 2048 --Dv 64 --T 200 --K 32 [--old-route]
                                                         (the codebook statistics / the quantizer's fused backward;
@@ -898,6 +903,101 @@ def bench_vq_bwd(a):
     _bench_vq_codebook(a, "vq_bwd")
 
 
+def bench_gauss_scenario(a):
+    """GaussianHMM.simulate (vqhmm_gauss_scenario_f32) at --B starts x --N paths x --T steps, S = --K states, --D
+    assets; --full: full covariances.  Two legs of the new call: final + drawdown only, and the same with x written.
+    --old-route: also what could be assembled before it: simulate_paths on log_A expanded to (B,T,S,S), torch.randn
+    (B,N,T,D), the gather of the means plus a scale multiply (diag) or S masked matmuls (full, GaussianHMM.sample's
+    way) for x, and torch ops (cumprod / cummax in fp64) for the wealth; five alternating pairs after a warm-up.
+    Every start has the same regime distribution (simulate_paths takes one log_pi), and the two routes draw
+    different random numbers, so the check line compares the two routes' mean and standard deviation of the final
+    wealth in units of their standard errors.  valu_frac: an instruction-count estimate of the kernel's arithmetic
+    (per Philox block 10 rounds of about 10 integer operations; per four normals about 100; the triangular or
+    diagonal fma's; 4 D for the fp64 wealth) over 256 CUs x 64 lanes x 2.4 GHz."""
+    B, N, H, S, D = a.B, a.N, a.T, a.K, a.D
+    kind = "full" if a.full else "diag"
+    gen = torch.Generator().manual_seed(3)
+    hmm = vqhmm.GaussianHMM(S, D, covariance_type=kind, generator=gen)
+    with torch.no_grad():
+        hmm.mean.mul_(1e-3)
+        if a.full:
+            Lc = torch.randn((S, D, D), generator=gen).tril(-1) * (0.4 / math.sqrt(D))
+            hmm.scale_tril.copy_(1e-2 * (Lc + torch.diag_embed(torch.rand((S, D), generator=gen) + 0.6)))
+        else:
+            hmm.log_var.copy_(2 * torch.log(1e-2 * (0.5 + torch.rand((S, D), generator=gen))))
+    hmm = hmm.cuda()
+    port = torch.rand((S, D), generator=gen)
+    port = (port / port.sum(1, keepdim=True)).cuda()
+    reb, tx = 5, 1e-3
+    state = torch.exp(hmm.log_pi.detach()).expand(B, S).contiguous()
+    start = hmm.predict_next(state)[0]
+    log_p0 = torch.log(start[0]).contiguous()
+    log_A = hmm.log_A.detach()
+    mean = hmm.mean.detach()
+    scale = hmm.scale_tril.detach().tril() if a.full else torch.exp(0.5 * hmm.log_var.detach())
+    tt = torch.arange(H, device="cuda")
+    last_reb = tt - tt % reb                       # the step whose regime's holdings are held at t
+    is_reb = (tt % reb == 0)
+
+    def new_final():
+        return hmm.simulate(H, N, state=state, seed=1, weights=port, rebalance=reb, tx_cost=tx)
+
+    def new_x():
+        return hmm.simulate(H, N, state=state, seed=1, weights=port, rebalance=reb, tx_cost=tx, return_x=True)
+
+    def old():
+        z = vqhmm.simulate_paths(log_p0, log_A.expand(B, H, S, S), n_samples=N).long()
+        eps = torch.randn((B, N, H, D), device="cuda")
+        if a.full:
+            x = mean[z]
+            for s in range(S):
+                x = x + (z == s).unsqueeze(-1) * (eps @ scale[s].T)
+        else:
+            x = torch.addcmul(mean[z], scale[z], eps)
+        hz = z[:, :, last_reb]
+        held = port[hz]
+        r = (held.double() * x.double()).sum(-1)
+        prev = torch.cat([torch.zeros_like(held[:, :, :1]), held[:, :, :-1]], 2)
+        turn = (held.double() - prev.double()).abs().sum(-1) * is_reb
+        w = torch.cumprod((1.0 - tx * turn) * (1.0 + r), -1)
+        peak = torch.cummax(w, -1).values.clamp_min(1.0)
+        return w[..., -1].float(), (1.0 - w / peak).amax(-1).clamp_min(0.0).float(), x
+
+    legs = {"gauss_scenario": new_final, "gauss_scenario_x": new_x}
+    dims = {"B": B, "N": N, "H": H, "S": S, "D": D, "full": a.full}
+    if a.old_route:
+        legs["old_route"] = old
+        res = new_x()
+        fo, do, xo = old()
+        torch.cuda.synchronize()
+        n = B * N
+        fn_, fo_ = res.final.double().flatten(), fo.double().flatten()
+        se_mean = math.sqrt((fn_.var().item() + fo_.var().item()) / n)
+        chk = {"final_mean": [fn_.mean().item(), fo_.mean().item()], "final_std": [fn_.std().item(), fo_.std().item()],
+               "final_mean_diff_in_se": abs(fn_.mean().item() - fo_.mean().item()) / se_mean,
+               "drawdown_mean": [res.drawdown.double().mean().item(), do.double().mean().item()],
+               "x_mean_maxdiff": (res.x.double().mean((0, 1, 2)) - xo.double().mean((0, 1, 2))).abs().max().item(),
+               "x_std_max_rel": ((res.x.double().std((0, 1, 2)) / xo.double().std((0, 1, 2))) - 1).abs().max().item()}
+        print(json.dumps(dict({"check": "old_route vs gauss_scenario"}, **dims, **chk)))
+        del res, fo, do, xo, fn_, fo_
+    rounds = _pairs(legs)
+    t = {k: sorted(v)[len(v) // 2] for k, v in rounds.items()}
+    nb = (D + 3) // 4
+    ops = B * N * H * ((1 + nb) * 100 + nb * 100 + (D * (D + 1) // 2 if a.full else D) + 4 * D)
+    for k in legs:
+        rec = dict({"kernel": k}, **dims, us=t[k] * 1e6, min_us=min(rounds[k]) * 1e6, max_us=max(rounds[k]) * 1e6,
+                   pairs_us=[r * 1e6 for r in rounds[k]])
+        if k == "old_route":
+            for new in ("gauss_scenario", "gauss_scenario_x"):
+                rec["x_" + new] = t[k] / t[new]
+                rec[new + "_faster_in_every_pair"] = all(o > f for o, f in zip(rounds[k], rounds[new]))
+        else:
+            byts = B * N * 8 + (B * N * H * D * 4 if k.endswith("_x") else 0)
+            rec.update(GBps=byts / t[k] / 1e9, frac_hbm=byts / t[k] / HBM_PEAK, valu_ops=ops,
+                       valu_frac=ops / t[k] / (256 * 64 * 2.4e9))
+        print(json.dumps(rec))
+
+
 def torch_ffbs(filt, log_A, u):
     """Plain-torch FFBS on full-length sequences, one step per iteration: a gather of the column
     z_t, a cumsum and a searchsorted (several launches per time step)."""
@@ -993,5 +1093,5 @@ if __name__ == "__main__":
      "gauss_estep_batched": bench_gauss_estep_batched,
      "gauss_moments": bench_gauss_moments, "code_fit": bench_code_fit, "code_viterbi": bench_code_viterbi,
      "code_filter": bench_code_filter, "gauss_viterbi": bench_gauss_viterbi, "gauss_filter": bench_gauss_filter,
-     "sample": bench_sample, "vq_stats": bench_vq_stats,
+     "sample": bench_sample, "vq_stats": bench_vq_stats, "gauss_scenario": bench_gauss_scenario,
      "vq_bwd": bench_vq_bwd}[a.what](a)

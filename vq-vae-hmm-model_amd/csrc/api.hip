@@ -639,6 +639,22 @@ int vqhmm_gauss_full_filter_f32(const float* log_pi, const float* log_A, const f
                                       loglik, (hipStream_t)stream);
 }
 
+int vqhmm_gauss_scenario_f32(const float* start, const float* log_A, const float* mean, const float* scale, int full,
+                             const float* port, int64_t rebalance, float tx_cost, uint64_t seed, int64_t b0,
+                             int64_t n0, int64_t B, int64_t N, int64_t H, int64_t S, int64_t D, int32_t* states,
+                             float* x, float* wealth, float* final_wealth, float* drawdown, void* stream) {
+  if (B < 0 || N < 0 || H < 0 || S < 0 || D < 0 || b0 < 0 || n0 < 0) return VQHMM_EINVAL;
+  if (!hmm_gauss_scenario_supported(B, N, H, S, D, full)) return VQHMM_EUNSUPPORTED;
+  if (B == 0 || N == 0 || H == 0) return VQHMM_OK;
+  if (!start || !log_A || !mean || !scale) return VQHMM_EINVAL;
+  if (!states && !x && !wealth && !final_wealth && !drawdown) return VQHMM_EINVAL;
+  if ((wealth || final_wealth || drawdown) && !port) return VQHMM_EINVAL;
+  const int64_t lim = int64_t(1) << 32;   // the counter words are 32 bits
+  if (rebalance < 1 || b0 > lim - B || n0 > lim - N) return VQHMM_EINVAL;
+  return launch_hmm_gauss_scenario(start, log_A, mean, scale, full, port, rebalance, tx_cost, seed, b0, n0, B, N, H,
+                                   S, D, states, x, wealth, final_wealth, drawdown, (hipStream_t)stream);
+}
+
 size_t vqhmm_vq_stats_workspace_size(int64_t B, int64_t Dv, int64_t T, int64_t K) {
   return vq_codebook_ws_bytes(B, Dv, T, K);
 }

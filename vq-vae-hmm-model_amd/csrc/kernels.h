@@ -598,6 +598,13 @@ int launch_hmm_gauss_full_viterbi(const float* log_pi, const float* log_A, const
 int launch_hmm_gauss_full_filter(const float* log_pi, const float* log_A, const float* mean, const float* prec_chol,
                                  const float* x, const int64_t* lengths, const float* prev, int64_t B, int64_t T,
                                  int64_t S, int64_t D, float* filt, float* last, float* loglik, hipStream_t s);
+// ... Monte Carlo scenarios of either Gaussian model with on-chip Philox (hmm_gauss_scenario.hip): start (B,S) ->
+// N paths of H steps per start; scale = sd (S,D) or, with full, L (S,D,D); every output nullable; no workspace
+bool hmm_gauss_scenario_supported(int64_t B, int64_t N, int64_t H, int64_t S, int64_t D, int full);
+int launch_hmm_gauss_scenario(const float* start, const float* log_A, const float* mean, const float* scale, int full,
+                              const float* port, int64_t rebalance, float tx_cost, uint64_t seed, int64_t b0,
+                              int64_t n0, int64_t B, int64_t N, int64_t H, int64_t S, int64_t D, int32_t* states,
+                              float* x, float* wealth, float* final_wealth, float* drawdown, hipStream_t s);
 // codebook learning (vq_codebook.hip), 1 <= K <= 65536, 1 <= Dv <= 512, K Dv <= 2^21: per-code count / residual
 // sum / sse in fp64 under given assignments (each nullable here), and with dz the quantizer's backward from the
 // same pass (dz = g_zq + *dz_scale r, dcb = *dcb_scale rsum from the reduce launch); ws = vq_codebook_ws_bytes.

@@ -19,8 +19,8 @@ from .checkpoint import load_checkpoint, load_encoder, save_checkpoint, save_enc
 from .codebook import Codebook  # noqa: E402,F401
 from .codehmm import CodeHMM, code_log_prob  # noqa: E402,F401
 from .codehmm_ensemble import CodeHMMEnsemble  # noqa: E402,F401
-from .gauss_hmm import (GaussianHMM, gauss_full_log_prob, gauss_log_prob, regime_covariance,  # noqa: E402,F401
-                        regime_moments)
+from .gauss_hmm import (GaussianHMM, Scenarios, gauss_full_log_prob, gauss_log_prob,  # noqa: E402,F401
+                        regime_covariance, regime_moments, scenario_summary)
 from .gauss_hmm_ensemble import GaussianHMMEnsemble  # noqa: E402,F401
 from .data import DeviceChunkLoader, RandomChunkDataset, collate_fn  # noqa: E402,F401
 from .hmm import (forward_backward, forward_filter, pairwise_posteriors, quantize, regime_argmax,  # noqa: E402,F401
@@ -34,5 +34,5 @@ __all__ = ["VAE_HMM", "Encoder", "Prior", "Decoder", "train_model", "Trainer", "
            "collate_fn", "DeviceChunkLoader", "vq_argmin", "quantize", "regime_argmax", "viterbi", "forward_backward", "PARAM_ORDER",
            "save_checkpoint", "load_checkpoint", "save_encoder", "load_encoder", "infer", "hard_regimes", "viterbi_regimes",
            "prior_viterbi", "forward_filter", "pairwise_posteriors", "filtered_regimes", "CodeHMM", "CodeHMMEnsemble", "code_log_prob", "Codebook", "GaussianHMM", "gauss_log_prob",
-           "gauss_full_log_prob", "regime_moments", "regime_covariance", "GaussianHMMEnsemble",
+           "gauss_full_log_prob", "regime_moments", "regime_covariance", "GaussianHMMEnsemble", "Scenarios", "scenario_summary",
            "sample_posterior_paths", "simulate_paths", "sampled_regimes", "simulate_regimes"]

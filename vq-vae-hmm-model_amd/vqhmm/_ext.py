@@ -98,6 +98,9 @@ _SIGS = {
                                                     c_vp, c_vp, c_vp, c_sz, c_vp]),
     "vqhmm_gauss_full_filter_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64,
                                                    c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "vqhmm_gauss_scenario_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.c_int, c_vp, c_i64, c_f32,
+                                                ctypes.c_uint64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64,
+                                                c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "vqhmm_vq_stats_workspace_size": (c_sz, [c_i64, c_i64, c_i64, c_i64]),
     "vqhmm_vq_stats_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp,
                                           c_sz, c_vp]),

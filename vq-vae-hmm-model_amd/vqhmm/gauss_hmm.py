@@ -18,6 +18,10 @@ filter with a carried (B,S) state, vqhmm_gauss_filter_f32 / vqhmm_gauss_full_fil
 
 Restarts (`fit(n_init=R)`) run on gauss_hmm_ensemble.GaussianHMMEnsemble, R models in one launch
 (vqhmm_gauss_estep_batched_f32 / vqhmm_gauss_full_estep_batched_f32).
+
+Looking forward from a filtered state: `simulate` (vqhmm_gauss_scenario_f32, hmm_gauss_scenario.hip) draws N
+scenario paths per start with the random numbers generated on chip (Philox4x32-10) and reduces a regime-dependent
+portfolio's wealth path to final wealth and maximum drawdown per path; `scenario_summary` is the table over them.
 """
 import torch
 
@@ -338,6 +342,32 @@ def regime_covariance(x, gamma, lengths=None):
     mu = c["m1"] / o[:, None]
     cov = c["m2"] / o[:, None, None] - mu[:, :, None] * mu[:, None, :]
     return mu + shift.double(), cov
+
+
+class Scenarios:
+    """What GaussianHMM.simulate returns: final (B,N), drawdown (B,N), wealth (B,N,H), states (B,N,H) int32 and x
+    (B,N,H,D); a field that was not computed is None."""
+    __slots__ = ("final", "drawdown", "wealth", "states", "x")
+
+    def __init__(self, final=None, drawdown=None, wealth=None, states=None, x=None):
+        self.final, self.drawdown, self.wealth, self.states, self.x = final, drawdown, wealth, states, x
+
+    def __repr__(self):
+        have = ", ".join(f"{k}={tuple(getattr(self, k).shape)}" for k in self.__slots__ if getattr(self, k) is not None)
+        return f"Scenarios({have})"
+
+
+def scenario_summary(final):
+    """final (B,N) final wealths of N paths per start -> dict of (B,) fp64 tensors on its device: mean, std
+    (unbiased), q05, q50, q95 (torch.quantile's linear interpolation) and prob_gain = P(final > 1).  NaN paths
+    (failed starts) make their start's row NaN."""
+    if not torch.is_tensor(final) or final.dim() != 2 or not final.dtype.is_floating_point:
+        raise ValueError("scenario_summary: final must be a floating point tensor of shape (B, N)")
+    f = final.detach().double()
+    q = torch.quantile(f, torch.tensor([0.05, 0.5, 0.95], dtype=torch.float64, device=f.device), dim=1)
+    gain = (f > 1).double().mean(1)
+    gain = torch.where(torch.isnan(f).any(1), torch.full_like(gain, float("nan")), gain)
+    return {"mean": f.mean(1), "std": f.std(1), "q05": q[0], "q50": q[1], "q95": q[2], "prob_gain": gain}
 
 
 class GaussianHMM(torch.nn.Module):
@@ -755,3 +785,54 @@ class GaussianHMM(torch.nn.Module):
                 for s in range(S):
                     x = x + (states == s).unsqueeze(-1) * (nr @ L[s].T)
         return states.long(), x
+
+    @torch.no_grad()
+    def simulate(self, horizon, n_paths, state=None, seed=0, weights=None, rebalance=1, tx_cost=0.0, return_x=False,
+                 return_states=False, return_wealth=False, start_offset=0, path_offset=0):
+        """Monte Carlo scenarios (vqhmm_gauss_scenario_f32, random numbers generated on chip): n_paths paths of
+        `horizon` steps from each of B starts -> Scenarios(final (B,N), drawdown (B,N), wealth (B,N,H), states
+        (B,N,H) int32, x (B,N,H,D)); what was not asked for is None.  `state` (B,S) fp32 is a filtered carry of
+        `filter` / `update`: simulated step 0 is the next observation, its regime drawn from predict_next(state)'s
+        probs; state=None: one start from exp(log_pi).  `weights` (S,D): the holdings taken when a rebalance (every
+        `rebalance` steps, from step 0) finds the path in that regime, at a cost of tx_cost per unit of turnover;
+        with weights, final wealth (start 1) and the maximum drawdown are returned, and with return_wealth the
+        whole wealth path.  Path (b, n) is path (start_offset + b, path_offset + n) of the seed's stream, so a
+        call on a slice of the starts or paths returns the full call's rows bit for bit.  Raises if nothing is
+        requested (no weights and neither return_x nor return_states)."""
+        _ext.require_device(self.log_pi)
+        H, N = int(horizon), int(n_paths)
+        S, D = self.num_states, self.dim
+        dev = self.log_pi.device
+        if H < 0 or N < 0:
+            raise ValueError("GaussianHMM.simulate: horizon and n_paths must be >= 0")
+        if weights is None and (return_wealth or not (return_x or return_states)):
+            raise ValueError("GaussianHMM.simulate: nothing to compute: pass weights (S, D) for final / drawdown / "
+                             "wealth, or ask for return_x / return_states")
+        if state is None:
+            start = torch.exp(self.log_pi.detach().double()).float().unsqueeze(0).contiguous()
+        else:
+            start = self.predict_next(state)[0].contiguous()
+        B = int(start.shape[0])
+        port = None
+        if weights is not None:
+            port = torch.as_tensor(weights).to(dev, torch.float32).contiguous()
+            if port.shape != (S, D):
+                raise ValueError(f"GaussianHMM.simulate: weights must have shape ({S}, {D})")
+        if self.full:
+            scale = self.scale_tril.detach().contiguous()
+        else:   # as the sampler: exp(log_var / 2) in fp64, rounded once
+            scale = torch.exp(0.5 * self.log_var.detach().double()).float().contiguous()
+
+        def buf(want, shape, dtype=torch.float32):
+            return torch.empty(shape, dtype=dtype, device=dev) if want else None
+
+        res = Scenarios(final=buf(port is not None, (B, N)), drawdown=buf(port is not None, (B, N)),
+                        wealth=buf(return_wealth, (B, N, H)), states=buf(return_states, (B, N, H), torch.int32),
+                        x=buf(return_x, (B, N, H, D)))
+        _ext.check(_ext.load().vqhmm_gauss_scenario_f32(
+            _ext.ptr(start), _ext.ptr(self.log_A.detach().contiguous()), _ext.ptr(self.mean.detach().contiguous()),
+            _ext.ptr(scale), int(self.full), _ext.ptr(port), int(rebalance), float(tx_cost),
+            int(seed) & 0xFFFFFFFFFFFFFFFF, int(start_offset), int(path_offset), B, N, H, S, D, _ext.ptr(res.states),
+            _ext.ptr(res.x), _ext.ptr(res.wealth), _ext.ptr(res.final), _ext.ptr(res.drawdown),
+            _ext.stream_ptr(dev)), "GaussianHMM.simulate")
+        return res
