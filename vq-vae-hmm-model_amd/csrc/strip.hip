@@ -1,17 +1,17 @@
 // Strip kernels: several convolution layers of the training step in ONE launch, the activations
 // between the layers kept in LDS (VQ_VAE_HMM_fixed.py:38-41 Encoder.forward, :80-90 Decoder.forward).
 //
-// A strip is a window of ST_WIN = 128 consecutive PCL rows whose middle ST_OWN = 124 rows it owns
-// (owned rows tile [0, R) without overlap).  Wave w of the 8-wave workgroup owns the window's
+// A strip is a window of ST_WIN = 128 consecutive PCL rows of which it owns the middle ones (the forward
+// strip SF_OWN = 122 from window row SF_LO = 3, below; the backward strip its middle ST_OWN = 124); the
+// owned rows tile [0, R) without overlap.  Wave w of the 8-wave workgroup owns the window's
 // 16-row block w through the whole chain
 //   x -> enc_conv1 -> enc_conv2 (+ to_logits, softmax) -> composed dec_conv1 -> dec_conv2 (+ to_params).
 // The narrow front convs (enc_conv1 on x, dec_conv1 on q: packed taps, 16 MFMAs a block) are computed
 // by the wave itself for the 18 rows its 64-wide conv reads (two overlapping MFMA blocks) into its own
 // LDS slot, so only q (and the next strip's x) cross waves: two workgroup barriers per strip.  The
-// window's outer rows are inexact after the k = 3 layers (x is loaded with a 2-row halo), so a strip
-// stores rows >= ST_HALO = 2 from its edges only: 3% recomputed rows replace four launches' fixed
-// costs (weight staging, the first tile's latency, the tail) with one — what bounds the step at the
-// strong-scaling shard sizes (B = 128 per GPU).
+// window's outer rows are inexact after the k = 3 layers, so a strip stores its owned rows only: 5%
+// recomputed rows replace four launches' fixed costs (weight staging, the first tile's latency, the
+// tail) with one — what bounds the step at the strong-scaling shard sizes (B = 128 per GPU).
 //
 // Every row goes through the pair launches' MFMA sequences and epilogue arithmetic (conv2_dev.h), so
 // the stored activations are the same bits as the conv2f path (tests: strip = pair launches).
@@ -40,6 +40,20 @@ struct StripFwdArgs {
 };
 
 namespace {
+
+// The forward strip's owned rows: window rows SF_LO .. SF_LO + SF_OWN - 1 = 3..124.  Each wave computes the front
+// convs for its own 16 window rows only (no blocks for the window's outer rows -1 and 128), so, with x loaded for
+// rows -1..128:
+//   h1e (enc_conv1)                  is exact on window rows 0..127,
+//   h2e, logits, q (enc_conv2, 1x1)  on rows 1..126,
+//   g1 (composed dec_conv1)          on rows 2..125,
+//   g2, mu | logvar (dec_conv2, 1x1) on rows 3..124: every owned row.
+// Slot 0's row 0 and slot 7's row 17 (h1e / g1 rows -1 and 128) are never written.  One MFMA column is one row, so
+// what they hold reaches only rows 0..2 and 125..127 of the later layers, which no strip stores; every layer's
+// stores are masked to the owned rows.  (The fused head reads q on rows 2..125: exact.)
+constexpr int SF_LO = 3;
+constexpr int SF_OWN = 122;
+static_assert(SF_LO >= 3 && SF_LO + SF_OWN - 1 <= ST_WIN - 4, "g2 / par are exact on window rows 3 .. ST_WIN - 4");
 
 template <int NB2>
 struct StripFwdLds {
@@ -91,19 +105,36 @@ __device__ __forceinline__ void pk_weights(const float* Wf, int C, int lg4, int 
   }
 }
 
+// The lane's gather of a packed-tap front's B operand, the same for every strip: k-column 4 lg4 + e reads the
+// word at off[e] = (l16 + tap) ST_XLD + c from its block's first input row; columns past 3C (in bit e clear)
+// read the row's first word and use 0.  The offsets come out of an empty asm so that they stay in registers
+// (the compiler otherwise rebuilds them from the taps, a multiply and an exec-masked region each, per block).
+struct PkGather {
+  int off[4];
+  unsigned in;
+  __device__ __forceinline__ void set(int C, int lg4, int l16) {
+    in = 0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int k = 4 * lg4 + e;
+      const bool ok = k < 3 * C;
+      const int tap = ok ? k / C : 0, c = ok ? k - tap * C : 0;
+      off[e] = (l16 + tap) * ST_XLD + c;
+      asm volatile("" : "+v"(off[e]));
+      in |= ok ? 1u << e : 0u;
+    }
+  }
+};
+
 // One packed-tap front MFMA block (c2_mfma_pk's sequence): 16 output rows whose k = 3 inputs are rows
-// Xw[l16 + tap] (stride ST_XLD); k-columns past 3C are 0 x 0.
-__device__ __forceinline__ void pk_block(const float (&w)[4][4], const float* Xw, int C, int lg4, int l16,
-                                         f32x4 (&acc)[4]) {
+// Xw[l16 + tap] (stride ST_XLD); k-columns past 3C are 0 x 0.  The four gathers are issued ahead of the MFMAs.
+__device__ __forceinline__ void pk_block(const float (&w)[4][4], const float* Xw, const PkGather& g, f32x4 (&acc)[4]) {
   float b[4];
 #pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const int k = 4 * lg4 + e;
-    const bool in = k < 3 * C;
-    const int tap = in ? k / C : 0, c = in ? k - tap * C : 0;
-    const float v = Xw[(l16 + tap) * ST_XLD + c];
-    b[e] = in ? v : 0.f;
-  }
+  for (int e = 0; e < 4; ++e) b[e] = Xw[g.off[e]];
+  __builtin_amdgcn_sched_barrier(0);  // all four reads in flight before the first is waited for
+#pragma unroll
+  for (int e = 0; e < 4; ++e) b[e] = (g.in >> e & 1u) ? b[e] : 0.f;
 #pragma unroll
   for (int nb = 0; nb < 4; ++nb) {
     acc[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -113,12 +144,11 @@ __device__ __forceinline__ void pk_block(const float (&w)[4][4], const float* Xw
 }
 
 // conv2_epilogue's ACT = 1 arithmetic on a 64-wide block (bias, ReLU, pad rows 0): rows r0 + l16;
-// rows l16 in [slo, shi) are stored to out (PCL, 64 channels); rows go to the LDS slot rows xs (every row,
-// or only row `only` when only >= 0), row 0 also to the row xlo and row 15 to the row xhi (when given).
+// rows l16 in [slo, shi) are stored to out (PCL, 64 channels); every row goes to the LDS slot rows xs,
+// row 0 also to the row xlo and row 15 to the row xhi (when given).
 __device__ __forceinline__ void front_epi(f32x4 (&acc)[4], const f32x4 (&bias)[4], int64_t r0, int64_t R, int T,
                                           int lg4, int l16, int slo, int shi, float* out, float* xs,
-                                          bool nostore, int only = -1, float* xlo = nullptr,
-                                          float* xhi = nullptr) {
+                                          bool nostore, float* xlo = nullptr, float* xhi = nullptr) {
   const int64_t r = r0 + l16;
   const bool valid = row_valid(r, R, T);
   const bool st = l16 >= slo && l16 < shi && r < R && !nostore;
@@ -132,7 +162,7 @@ __device__ __forceinline__ void front_epi(f32x4 (&acc)[4], const f32x4 (&bias)[4
     }
     acc[nb] = y;
     if (st) *reinterpret_cast<f32x4*>(out + r * 64 + nb * 16 + 4 * lg4) = y;
-    if (only < 0 || l16 == only) *reinterpret_cast<f32x4*>(xs + l16 * ST_LDW + nb * 16 + 4 * lg4) = y;
+    *reinterpret_cast<f32x4*>(xs + l16 * ST_LDW + nb * 16 + 4 * lg4) = y;
     if (xlo && l16 == 0) *reinterpret_cast<f32x4*>(xlo + nb * 16 + 4 * lg4) = y;
     if (xhi && l16 == 15) *reinterpret_cast<f32x4*>(xhi + nb * 16 + 4 * lg4) = y;
   }
@@ -272,8 +302,8 @@ __global__ __launch_bounds__(512) void strip_fwd_kernel(StripFwdArgs a, HeadArgs
   const int T = a.T, ldx = ld4(a.D);
   float* slot = sh.slot[wave];
 
-  // x rows s0 - 2 .. s0 + 129 of a window: thread i < 2 ST_XR holds float4 i % 2 of row i / 2;
-  // the load is unconditional (clamped), the mask applied when it is stored
+  // x rows s0 - 2 .. s0 + 129 of a window (enc_conv1 reads s0 - 1 .. s0 + 128 of them): thread i < 2 ST_XR holds
+  // float4 i % 2 of row i / 2; the load is unconditional (clamped), the mask applied when it is stored
   auto load_x = [&](int64_t s0) {
     const int row = tid >> 1, h = 4 * (tid & 1);
     int64_t r = s0 - 2 + row;
@@ -323,8 +353,9 @@ __global__ __launch_bounds__(512) void strip_fwd_kernel(StripFwdArgs a, HeadArgs
   stamp<PROF>(0);
   if constexpr (PROF > 0) { if (threadIdx.x == 0 && blockIdx.x < 256) g_prof[blockIdx.x * 16 + 13] = __builtin_amdgcn_s_memtime(); }
   // ---- once.  vmcnt retires in order, so: the front images (LDS DMA) first, then x and the epilogue
-  // constants (registers), then the two 64-wide images (LDS DMA): waiting for x / the constants never
-  // waits for the big images, which stay in flight through the first enc_conv1.
+  // constants (registers), and the two 64-wide images (LDS DMA, outside the compiler's count) only after x and
+  // the constants have arrived and gone to LDS: a counted wait with these behind it would wait for them too.
+  // They stay in flight through the first enc_conv1.
   // Wf[img][row][8] <- image row (tap, n) channels 0..7, by waves 0..3 only: those store x before the
   // first barrier, so their wait for x (younger) covers these
   for (int j = wave; wave < 4 && j < 12; j += 4) {
@@ -332,7 +363,7 @@ __global__ __launch_bounds__(512) void strip_fwd_kernel(StripFwdArgs a, HeadArgs
     dma16((img ? a.img_d1 : a.img_e1) + row * ST_LDF + h, &sh.Wf[0][0] + j * 256);
   }
   int64_t s = blockIdx.x;
-  float4 px = load_x(s * ST_OWN - ST_HALO);
+  float4 px = load_x(s * SF_OWN - SF_LO);
   constexpr int NE = NW2 * 17 + 16, ND = 64 * 17 + 16, NC = NE + ND + 128;  // sh.Ee2 | sh.Ed2 | sh.bf
   constexpr int NCJ = (NC + 511) / 512;
   float cv[NCJ];
@@ -352,21 +383,6 @@ __global__ __launch_bounds__(512) void strip_fwd_kernel(StripFwdArgs a, HeadArgs
   }
 #pragma unroll
   for (int j = 0; j < NCJ; ++j) cv[j] = cvok[j] ? cv[j] : 0.f;
-  {
-    constexpr int N1 = 3 * NW2 * ST_LDW / 4, N2 = 3 * 64 * ST_LDW / 4;  // float4s of each image
-    constexpr int C1 = (N1 + 63) / 64, C2 = (N2 + 63) / 64;              // one wave instruction = 1 KB
-    // a fixed count per wave (the last chunk copied again where a wave has fewer: the same bytes), so the
-    // compiler counts these in vmcnt and its waits for x / the constants below leave them in flight
-    constexpr int NJ = (C1 + C2 + 7) / 8;
-#pragma unroll
-    for (int jj = 0; jj < NJ; ++jj) {
-      const int c = min(wave + 8 * jj, C1 + C2 - 1);
-      const bool first = c < C1;
-      const int cc = first ? c : c - C1;
-      const int i = cc * 64 + lane;
-      if (i < (first ? N1 : N2)) dma16((first ? a.img_e2 : a.img_d2) + 4 * i, (first ? sh.We2 : sh.Wd2) + cc * 256);
-    }
-  }
   static_assert(offsetof(S, Ed2) == offsetof(S, Ee2) + NE * 4, "constant blocks must be contiguous");
 #pragma unroll
   for (int j = 0; j < NCJ; ++j) {
@@ -375,12 +391,34 @@ __global__ __launch_bounds__(512) void strip_fwd_kernel(StripFwdArgs a, HeadArgs
     else if (i < NC) sh.bf[0][i - NE - ND] = cv[j];
   }
   if (tid < 4 * ST_XLD) sh.Xq[(tid < 2 * ST_XLD ? 0 : (ST_XR - 4) * ST_XLD) + tid] = 0.f;  // rows never written
-  store_x(s * ST_OWN - ST_HALO, px);
+  store_x(s * SF_OWN - SF_LO, px);
+  {
+    constexpr int N1 = 3 * NW2 * ST_LDW / 4, N2 = 3 * 64 * ST_LDW / 4;  // float4s of each image
+    constexpr int C1 = (N1 + 63) / 64, C2 = (N2 + 63) / 64;              // one wave instruction = 1 KB
+    static_assert(N1 >= 64 && N2 >= 64, "a chunk is a whole KB inside its image");
+    // whole 1-KB chunks, every lane active, a fixed count per wave (the last chunk copied again where a wave has
+    // fewer: the same bytes).  An image's last chunk starts at its last whole KB (the one-block enc_conv2 image
+    // is 13.5 KB: its chunk 13 overlaps chunk 12 by half, the same bytes again), so nothing past an image is
+    // read and nothing past its LDS copy written.  Outside the compiler's vmcnt count (strip_dev.h): the loop
+    // below has no wait that these would turn into a drain, and the first strip waits for them by hand.
+    constexpr int NJ = (C1 + C2 + 7) / 8;
+    const int wv = __builtin_amdgcn_readfirstlane(wave);
+#pragma unroll
+    for (int jj = 0; jj < NJ; ++jj) {
+      const int c = min(wv + 8 * jj, C1 + C2 - 1);
+      const bool first = c < C1;
+      const int i0 = first ? min(c * 64, N1 - 64) : min((c - C1) * 64, N2 - 64);  // the chunk's first float4
+      dma16_uncounted((first ? a.img_e2 : a.img_d2) + 4 * i0, 16 * lane, (first ? sh.We2 : sh.Wd2) + 4 * i0);
+    }
+  }
   lds_barrier();  // LDS only: the big images stay in flight (the front images are older than x: landed)
   stamp<PROF>(1);
   float wE[4][4], wD[4][4];
   pk_weights(sh.Wf[0], a.D, lg4, l16, wE);
   pk_weights(sh.Wf[1], a.K, lg4, l16, wD);
+  PkGather gE, gD;
+  gE.set(a.D, lg4, l16);
+  gD.set(a.K, lg4, l16);
   f32x4 bE[4], bD[4];
 #pragma unroll
   for (int nb = 0; nb < 4; ++nb) {
@@ -421,37 +459,31 @@ __global__ __launch_bounds__(512) void strip_fwd_kernel(StripFwdArgs a, HeadArgs
   float s_rec = 0.f, s_ent = 0.f, s_tr = 0.f, s_init = 0.f, q0acc = 0.f, db2acc = 0.f;
   f32x4 gW2 = f32x4{0.f, 0.f, 0.f, 0.f}, gW1 = gW2;  // this wave's hidden block (hb = wave, HB <= 8)
 
-  // this wave's block: window rows 16 w .. 16 w + 15 in every layer.  Stored rows (window rows ST_HALO ..
-  // ST_HALO + ST_OWN - 1): l16 in [slo, shi)
-  const int mlo = ST_HALO - 16 * wave, mhi = ST_HALO + ST_OWN - 16 * wave;  // in block-row units
+  // this wave's block: window rows 16 w .. 16 w + 15 in every layer.  Stored rows (window rows SF_LO ..
+  // SF_LO + SF_OWN - 1): l16 in [slo, shi)
+  const int mlo = SF_LO - 16 * wave, mhi = SF_LO + SF_OWN - 16 * wave;  // in block-row units
   const int slo = max(0, mlo), shi = min(16, mhi);
   const bool nost = a.dbg & 1;
   int it = 0;
   for (; s < a.nstrip; s += gridDim.x) {
-    const int64_t s0 = s * ST_OWN - ST_HALO;  // PCL row of window row 0
-    const int64_t rb = s0 + 16 * wave;        // PCL row of this wave's block row 0
+    const int64_t s0 = s * SF_OWN - SF_LO;  // PCL row of window row 0
+    const int64_t rb = s0 + 16 * wave;      // PCL row of this wave's block row 0
     {
       const int64_t nx = s + gridDim.x;
-      px = load_x((nx < a.nstrip ? nx : s) * ST_OWN - ST_HALO);  // the next strip's x, in flight
+      px = load_x((nx < a.nstrip ? nx : s) * SF_OWN - SF_LO);  // the next strip's x, in flight
     }
     // ---- enc_conv1 + ReLU for rows rb .. rb + 15 (h1e: owned rows) -> slot rows 1..16, row rb to the
-    // previous wave's slot row 17, row rb + 15 to the next wave's slot row 0; the window's outer rows -1
-    // and 128 (slot 0 row 0, slot 7 row 17) by waves 5 and 6 (SIMDs 1 and 2: no SIMD runs three blocks
-    // twice as long as another)
+    // previous wave's slot row 17, row rb + 15 to the next wave's slot row 0.  No blocks for the window's
+    // outer rows -1 and 128 (slot 0 row 0, slot 7 row 17): the owned rows do not need them (SF_LO above)
     {
       f32x4 acc[4];
-      pk_block(wE, sh.Xx + (16 * wave + 1) * ST_XLD, a.D, lg4, l16, acc);
-      front_epi(acc, bE, rb, R, T, lg4, l16, slo, shi, a.h1e, slot + ST_LDW, nost, -1,
+      pk_block(wE, sh.Xx + (16 * wave + 1) * ST_XLD, gE, acc);
+      front_epi(acc, bE, rb, R, T, lg4, l16, slo, shi, a.h1e, slot + ST_LDW, nost,
                 wave > 0 ? sh.slot[wave - 1] + 17 * ST_LDW : nullptr, wave < 7 ? sh.slot[wave + 1] : nullptr);
-      if (wave == 5 || wave == 6) {
-        const bool lo = wave == 5;
-        f32x4 acc2[4];
-        pk_block(wE, sh.Xx + (lo ? 0 : 16 * 7 + 2) * ST_XLD, a.D, lg4, l16, acc2);
-        front_epi(acc2, bE, lo ? s0 - 1 : s0 + 16 * 7 + 1, R, T, lg4, l16, 0, 0, a.h1e,
-                  lo ? sh.slot[0] : sh.slot[7] + 2 * ST_LDW, true, lo ? 0 : 15);
-      }
     }
-    if (it == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the first strip: the image DMA
+    // the first strip: the image DMA.  The compiler does not know of it (dma16_uncounted), so this wait is the
+    // only thing that orders the images ahead of the barrier that publishes them
+    if (it == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     lds_barrier();  // every slot's rows (and, first strip, every wave's share of the images)
     // ---- enc_conv2 + ReLU (h2e) + to_logits (logits) + softmax (q; all 16 rows -> Xq)
     {
@@ -479,20 +511,18 @@ __global__ __launch_bounds__(512) void strip_fwd_kernel(StripFwdArgs a, HeadArgs
     // ---- composed dec_conv1 + ReLU for rows rb .. rb + 15 (g1: owned rows) -> slots, as enc_conv1
     {
       f32x4 acc[4];
-      pk_block(wD, sh.Xq + (16 * wave + 1) * ST_XLD, a.K, lg4, l16, acc);
+      pk_block(wD, sh.Xq + (16 * wave + 1) * ST_XLD, gD, acc);
       if constexpr (PROF > 0) {
         if (it == 0) {
           asm volatile("s_nop 0" : : "v"(acc[3][3]));
           stamp<PROF>(10);
         }
       }
-      front_epi(acc, bD, rb, R, T, lg4, l16, slo, shi, a.g1, slot + ST_LDW, nost, -1,
+      front_epi(acc, bD, rb, R, T, lg4, l16, slo, shi, a.g1, slot + ST_LDW, nost,
                 wave > 0 ? sh.slot[wave - 1] + 17 * ST_LDW : nullptr, wave < 7 ? sh.slot[wave + 1] : nullptr);
       if (it == 0) stamp<PROF>(11);
-      // no blocks for the window's outer g1 rows -1 and 128 (slot 0 row 0, slot 7 row 17), unlike enc_conv1:
-      // they reach only dec_conv2's window rows 0 and 127, which no strip stores (g2 / par go out for rows
-      // ST_HALO .. ST_HALO + ST_OWN - 1 and nothing later reads the slots).  One MFMA column is one row, so
-      // whatever enc_conv1 left in those two slot rows stays inside the discarded rows.
+      // no blocks for the window's outer g1 rows -1 and 128 either: they reach only dec_conv2's window rows 0
+      // and 127, which no strip stores, and nothing later reads the slots
     }
     lds_barrier();  // every slot's rows
     if (it == 0) stamp<PROF>(4);
@@ -511,37 +541,41 @@ __global__ __launch_bounds__(512) void strip_fwd_kernel(StripFwdArgs a, HeadArgs
           stamp<PROF>(5);
         }
       }
+      // the next strip's x (Xx is free: every wave passed the q barrier after its last read).  Here, ahead of the
+      // epilogue's stores: the wait for px cannot be counted past the stores issued since its load (they sit
+      // under lane-divergent branches), so it drains them, and the youngest at this point are g1's, a whole
+      // 192-MFMA loop old.  After the epilogue it waited for the round trip of g2 / par, just issued.
+      {
+        const int64_t nx = s + gridDim.x;
+        store_x((nx < a.nstrip ? nx : s) * SF_OWN - SF_LO, px);
+      }
       if constexpr (HTH > 0) kD.load(sh.Ed2, lg4, l16);
       tail_epi<4, false>(y, kD, rb, R, T, lg4, l16, slo, shi, 64, a.g2, a.P, a.par, nullptr, nullptr, nost);
     }
     if (it == 0) stamp<PROF>(6);
-    // the next strip's x (Xx is free: every wave passed the barrier after its last read)
-    {
-      const int64_t nx = s + gridDim.x;
-      store_x((nx < a.nstrip ? nx : s) * ST_OWN - ST_HALO, px);
-    }
     if constexpr (HTH > 0) __syncthreads();  // + mu | logvar (HBM) of every block, for the head
     else lds_barrier();                      // Xx written; Xq and the slots free again
     if (it == 0) stamp<PROF>(3);
     if constexpr (HTH > 0) {
-      // ================= fused ELBO head on window rows ST_HALO .. ST_HALO + ST_OWN (the last one = the
+      // ================= fused ELBO head on window rows SF_LO .. SF_LO + SF_OWN (the last one = the
       // halo row whose log_A the last owned row's t -> t+1 term needs): head_coop.hip's phases, WR = 128
       StripHeadLds& hs = *reinterpret_cast<StripHeadLds*>(&sh.slot[0][0]);
       const StripHeadW<HTH>& hw = *reinterpret_cast<const StripHeadW<HTH>*>(&sh.Wf[0][0]);
       constexpr int LDL = StripHeadLds::LDL;
       const int K = h.K, U = h.U, D = h.D, KK = K * K;
       const int ldp = ld4(2 * D), ldxh = ld4(D), ldu = ld4(U);
-      const int64_t r = s0 + ST_HALO + prow;
+      const int64_t r = s0 + SF_LO + prow;
       const unsigned Tp = (unsigned)T + 2u;
       const unsigned rcl = (unsigned)(r < R ? r : R - 1);
       const int b = (int)(rcl / Tp);
       const int t = (int)(rcl - (unsigned)b * Tp) - 1;
-      const bool valid = r < R && prow <= ST_OWN && t >= 0 && t < T;
-      const bool own = prow < ST_OWN && r < R;
+      const bool valid = r < R && prow <= SF_OWN && t >= 0 && t < T;
+      const bool own = prow < SF_OWN && r < R;
       const int64_t L = h.lengths[b];
       const bool m = valid && t < L;
       const float wgt = (valid && t >= 1 && t < L) ? 1.f : 0.f;  // pair (t-1, t) inside the length
-      const float* qrow = sh.Xq + (ST_HALO + prow + 2) * ST_XLD;  // q | logits of the row
+      // q | logits of the row (rows past the head's SF_OWN + 1 are not used: kept inside Xq)
+      const float* qrow = sh.Xq + min(SF_LO + prow + 2, ST_XR - 1) * ST_XLD;
       float qv[HKP];
 #pragma unroll
       for (int k = 0; k < HKP; ++k) qv[k] = (valid && k < K) ? qrow[k] : 0.f;
@@ -979,7 +1013,7 @@ static StripFwdArgs strip_fwd_args(const ConvArgs& e1, const ConvArgs& e2, const
   a.b_e1 = e1.bias; a.b_e2 = e2.bias; a.b_d1 = d1.bias; a.b_d2 = d2.bias;
   a.tWl = e2.tW; a.tbl = e2.tb; a.tWp = d2.tW; a.tbp = d2.tb;
   a.h1e = e1.out; a.h2e = e2.out; a.logits = e2.t_out; a.q = e2.q_out; a.g1 = d1.out; a.g2 = d2.out; a.par = d2.t_out;
-  a.nstrip = cdiv(e1.R, ST_OWN);
+  a.nstrip = cdiv(e1.R, SF_OWN);
   static const int dbg = [] {
     const char* e = VQHMM_PROF_ENV("VQHMM_STRIP_DBG");
     return e ? atoi(e) : 0;
@@ -1007,7 +1041,7 @@ bool strip_head_supported(const HeadArgs& h) {
 }
 
 int strip_fwd_grid(int64_t R) {
-  const int64_t n = cdiv(R, ST_OWN);
+  const int64_t n = cdiv(R, SF_OWN);
   return (int)(n < 256 ? (n > 0 ? n : 1) : 256);
 }
 

@@ -233,22 +233,7 @@ __device__ __forceinline__ void wg_pass(int nstep, ldsp pa, ldsp pb, int ga, int
   }
 }
 
-// dma16 kept out of the compiler's count of memory operations.  While a global_load_lds it knows of is
-// outstanding in vmcnt, the compiler takes lgkmcnt for out of order as well (the instruction is FLAT-encoded
-// and has an LDS operand) and turns every wait for an LDS read into lgkmcnt(0): dec_conv2's pass in P2, which
-// runs under the image's DMA, then waited for the reads it had just issued on every other step.  The caller
-// waits for these with its own vmcnt; loads the compiler counts wait at most longer for being counted short.
-// One 1-KB chunk per wave: lane l copies the 16 bytes at src + off (off = 16 l) to dst + 16 l; src and dst are
-// wave-uniform.  (s_nop 4: an SGPR written by a VALU instruction just ahead is not read early as an address.)
-__device__ __forceinline__ void dma16_uncounted(const float* src, int off, float* dst) {
-  const unsigned d = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) float*)dst);
-  unsigned keep;
-  asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-               "global_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(off), "s"(d), "s"(src)
-               : "memory");
-}
+// (dma16_uncounted, the LDS DMA issued outside the compiler's vmcnt bookkeeping: strip_dev.h)
 
 // the lane-group partials of a bias column summed in a fixed order: (g0 + g1) + (g2 + g3) on every lane
 __device__ __forceinline__ float col_sum4(float v) {

@@ -35,6 +35,25 @@ __device__ __forceinline__ void dma16(const float* src, float* dst) {
                                    16, 0, 0);
 }
 
+// dma16 kept out of the compiler's count of memory operations.  While a global_load_lds it knows of is
+// outstanding in vmcnt, the compiler takes lgkmcnt for out of order as well (the instruction is FLAT-encoded
+// and has an LDS operand) and turns every wait for an LDS read into lgkmcnt(0): dec_conv2's pass in the folded
+// backward strip's P2, which runs under the image's DMA, then waited for the reads it had just issued on every
+// other step.  It also drains vmcnt ahead of every LDS read that may alias the destination: the forward strip's
+// loop header waited for the previous strip's stores on every wave.  The caller waits for these with its own
+// vmcnt; loads the compiler counts wait at most longer for being counted short.
+// One 1-KB chunk per wave: lane l copies the 16 bytes at src + off (off = 16 l) to dst + 16 l; src and dst are
+// wave-uniform.  (s_nop 4: an SGPR written by a VALU instruction just ahead is not read early as an address.)
+__device__ __forceinline__ void dma16_uncounted(const float* src, int off, float* dst) {
+  const unsigned d = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) float*)dst);
+  unsigned keep;
+  asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
+               "global_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep)
+               : "v"(off), "s"(d), "s"(src)
+               : "memory");
+}
+
 // conv2_epilogue's ACT = 2 arithmetic (scale, no bias, ReLU-backward mask, pad rows 0) on a 64-wide
 // block: rows r0 + l16, stored (PCL, 64 channels) for l16 in [slo, shi) when out is set, optionally to LDS
 // rows xs (every row, or only row `only` when only >= 0), row 0 also to the row xlo and row 15 to the row
