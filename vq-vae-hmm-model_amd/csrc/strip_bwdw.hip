@@ -120,6 +120,12 @@ __device__ __forceinline__ void c2_tile_n4(const float* Wc, const float* Xw, int
 // An LDS address: 32-bit arithmetic, and a constant index becomes the read's immediate offset
 typedef const __attribute__((address_space(3))) float* ldsp;
 __device__ __forceinline__ ldsp to_lds(const float* p) { return (ldsp)p; }
+// A global load addressed as a wave-uniform base plus a 32-bit per-lane byte offset plus a constant (the
+// instruction's scalar-base form: no 64-bit per-lane address arithmetic); off >= 0
+template <class V>
+__device__ __forceinline__ V ld_so(const float* sbase, int off, int imm = 0) {
+  return *reinterpret_cast<const V*>(reinterpret_cast<const char*>(sbase) + (unsigned)off + imm);
+}
 enum { SEL_NONE = 0, SEL_A = 1, SEL_B = 2 };  // which operand of a pass has structurally-zero lanes
 
 // One wave's tiles of a weight gradient over the owned window rows: nstep 4-row steps, one MFMA per tile per
@@ -211,6 +217,69 @@ __device__ __forceinline__ void wg_pass(int nstep, ldsp pa, ldsp pb, int ga, int
     return;
   }
   // two sets: the next step's operands are read while this step's NT MFMAs run
+  load(0);
+  int k = 0;  // set 0 holds step k, the group's step 0
+  for (; k + 5 <= nstep; k += 4) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (j == 3) next();
+      load((j + 1) & 3);  // step k + j + 1
+      __builtin_amdgcn_sched_barrier(0);
+      mma(j);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+  const int rem = nstep - k;  // 1..4 steps left, the first of them read
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    if (j < 3 && j + 1 < rem) load(j + 1);
+    __builtin_amdgcn_sched_barrier(0);
+    if (j < rem) mma(j);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+// wg_pass<NT>'s two-set form with one more, independent tile riding in the same steps: its own operands (pc / pd
+// moving by gc / gd per group, read by fc / fd), its A operand structurally zero where okx is false (SEL_A, the
+// select where the word is used), its own accumulator and bias partial.  The tile sees the rows and the k order
+// of a wg_pass<1, SEL_A> of its own, so the same sums: the pass it replaces was a 32-cycle dependent chain on
+// two waves with the other six waiting at the barrier.
+template <int NT, class FA, class FB, class FC, class FD>
+__device__ __forceinline__ void wg_pass_x(int nstep, ldsp pa, ldsp pb, int ga, int gb, FA fa, FB fb, f32x4 (&acc)[NT],
+                                          float& bacc, ldsp pc, ldsp pd, int gc, int gd, FC fc, FD fd, bool okx,
+                                          f32x4& accx, float& baccx) {
+  float ar[2], br[2][NT], cr[2], dr[2];
+  auto hide = [](ldsp& p) __attribute__((always_inline)) { asm volatile("" : "+v"(p)); };
+  auto load = [&](int j) __attribute__((always_inline)) {
+    ar[j % 2] = fa(pa, j);
+#pragma unroll
+    for (int t = 0; t < NT; ++t) br[j % 2][t] = fb(pb, j, t);
+    cr[j % 2] = fc(pc, j);
+    dr[j % 2] = fd(pd, j);
+  };
+  auto next = [&]() __attribute__((always_inline)) {
+    pa += ga;
+    pb += gb;
+    pc += gc;
+    pd += gd;
+    hide(pa);
+    hide(pb);
+    hide(pc);
+    hide(pd);
+  };
+  hide(pa);
+  hide(pb);
+  hide(pc);
+  hide(pd);
+  auto mma = [&](int j) __attribute__((always_inline)) {
+    const float av = ar[j % 2];
+    bacc += av;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) acc[t] = mfma16x16x4(av, br[j % 2][t], acc[t]);
+    const float cv = okx ? cr[j % 2] : 0.f;
+    baccx += cv;
+    accx = mfma16x16x4(cv, dr[j % 2], accx);
+  };
   load(0);
   int k = 0;  // set 0 holds step k, the group's step 0
   for (; k + 5 <= nstep; k += 4) {
@@ -414,13 +483,19 @@ __global__ __launch_bounds__(512) void strip_bwdw_kernel(SWArgs a, ConvArgs f) {
     if (lg4 == 0) a.bslab[5][ch * 64 + ob * 16 + l16] = cb;
   };
 
+  // what a lane keeps across the strips (32-bit each; the strip's addresses are scalar bases + these)
+  const int rm = ((lg4 & 1) << 1) | (lg4 >> 1);  // rows 2 apart in each 32-lane half: conflict-free b32 reads
+  const int row0 = lo + rm;  // this lane's window row in a weight-gradient pass's step 0 (step k: row0 + 4 k)
+  const int qtap = l16 / K, qc = l16 - qtap * K;
+  const bool qok = l16 < 3 * K;
+  const int xtap = l16 / D, xc = l16 - xtap * D;
+  const bool xok = l16 < 3 * D;
+  const int wrow = 16 * wave + l16;  // this lane's window row in the dgrad blocks
+  const int xsh = ld4(D) == 8 ? 1 : 0;
+
   int it = 0;
   for (int64_t s = blockIdx.x; s < a.nstrip; s += gridDim.x) {
     const bool last = s + gridDim.x >= a.nstrip;  // this workgroup's last strip: P7 stages the dE share
-    // the lane ids re-derived opaquely per strip: the per-lane addresses below are recomputed here instead of
-    // being hoisted out of the loop as 64-bit VGPR pairs (the accumulators need those registers)
-    int tidv = tid;
-    asm volatile("" : "+v"(tidv));
     // the profiled strip's start (VQHMM_STRIP_PROF_IT): the clock is read here and stored after B1.  Stored here,
     // the stamp sat in front of the loop header's vmcnt(0) and P1's loads were issued only after its round trip
     [[maybe_unused]] unsigned long long t15 = 0;
@@ -429,38 +504,43 @@ __global__ __launch_bounds__(512) void strip_bwdw_kernel(SWArgs a, ConvArgs f) {
     // of P1's loads: waited with them.  Loaded once before the loop they cost the first strip a vmcnt(0)
     // (a register copy of the value) that also waited for the compact image's DMA
     // (unconditional: a null pointer selects the device constant 1; a branch per load would join before the DMA)
-    const int z0 = tidv >> 10;  // 0 (tidv < 512), opaque to the compiler
+    int z0 = 0;  // an opaque zero index
+    asm volatile("" : "+v"(z0));
     const float psc = (a.gscale ? a.gscale : &g_bwdw_one)[z0];
     const float fsc = (f.scale ? f.scale : &g_bwdw_one)[z0];
     const float lsc = (f.lb_scale ? f.lb_scale : &g_bwdw_one)[z0];
-    const int lane = tidv & 63, lg4 = lane >> 4, l16 = lane & 15;
-    const int rm = ((lg4 & 1) << 1) | (lg4 >> 1);  // rows 2 apart in each 32-lane half: conflict-free b32 reads
-    const int row0 = lo + rm;  // this lane's window row in a weight-gradient pass's step 0 (step k: row0 + 4 k)
-    const int qtap = l16 / K, qc = l16 - qtap * K;
-    const bool qok = l16 < 3 * K;
-    const int xtap = l16 / D, xc = l16 - xtap * D;
-    const bool xok = l16 < 3 * D;
     const int64_t s0 = s * own - SW_LO;  // PCL row of window row 0
     const int64_t rb = s0 + 16 * wave;
-    // dpar row r, channels 4 lg4 ..: the raw load from a clamped address, and its mask (rows outside / pad
+    // Every row-indexed load of the strip is a per-strip scalar base (the array's row s0: SALU) plus a 32-bit
+    // per-lane byte offset, the lane's window row clamped into [0, R) against two per-strip scalars: window
+    // rows wlo .. whi are the rows inside (s0 >= -SW_LO and s0 <= R - 4, so 0 <= wlo <= 3 <= whi <= 127)
+    const int wlo = s0 < 0 ? (int)-s0 : 0;
+    const int whi = R - 1 - s0 < ST_WIN - 1 ? (int)(R - 1 - s0) : ST_WIN - 1;
+    auto clampw = [&](int w) { return min(max(w, wlo), whi); };
+    const int cw = clampw(wrow);      // the clamped window row of PCL row rb + l16
+    const bool inr = cw == wrow;      // that row is inside [0, R)
+    const int off64 = cw * 256 + 16 * lg4;  // bytes: channels 4 lg4 .. of a 64-channel row (+ 64 nb)
+    auto ldw = [&](const float* m, float4 (&aux)[4]) __attribute__((always_inline)) {  // load_mask's rows
+      const float* sb = m + s0 * 64;
+#pragma unroll
+      for (int nb = 0; nb < 4; ++nb) aux[nb] = ld_so<float4>(sb, off64, 64 * nb);
+    };
+    // dpar row rb + l16, channels 4 lg4 ..: the raw load from a clamped address, and its mask (rows outside / pad
     // channels 0) applied where it is used, so no wait sits right behind the load
-    auto ld_dpar_raw = [&](int64_t r) {
-      const int64_t rc = r < 0 ? 0 : (r >= R ? R - 1 : r);
-      return *reinterpret_cast<const float4*>(a.dpar + rc * a.ldp + min(4 * lg4, a.ldp - 4));
-    };
-    auto dpar_mask = [&](int64_t r, float4 v) {
-      return (r >= 0 && r < R && 4 * lg4 < a.ldp) ? v : make_float4(0.f, 0.f, 0.f, 0.f);
-    };
+    auto ld_dpar_raw = [&]() { return ld_so<float4>(a.dpar + s0 * a.ldp, 4 * (cw * a.ldp + min(4 * lg4, a.ldp - 4))); };
+    auto dpar_mask = [&](float4 v) { return (inr && 4 * lg4 < a.ldp) ? v : make_float4(0.f, 0.f, 0.f, 0.f); };
     // ================= P1: the 1x1 to_params dgrad -> slots (as strip_bwd_kernel); G1 <- g1; Q <- q
     float4 m1[4];
     {
-      float wP[4][4];  // A operand of the 1x1 front: image[n = nb*16 + l16][k = 4 lg4 + e] (L2)
+      // A operand of the 1x1 front: image[n = nb*16 + l16][k = 4 lg4 + e] (L2).  Kept across the strips, its 16
+      // registers are live through P2, the kernel's fullest phase, and two values spill
+      float wP[4][4];
 #pragma unroll
       for (int nb = 0; nb < 4; ++nb) {
-        const float4 w4 = *reinterpret_cast<const float4*>(a.img_pd + (nb * 16 + l16) * ST_LDF + 4 * lg4);
+        const float4 w4 = ld_so<float4>(a.img_pd, 4 * (l16 * ST_LDF + 4 * lg4), nb * 16 * ST_LDF * 4);
         wP[nb][0] = w4.x; wP[nb][1] = w4.y; wP[nb][2] = w4.z; wP[nb][3] = w4.w;
       }
-      load_mask(a.g1, rb, R, lg4, l16, m1);
+      ldw(a.g1, m1);
       auto front = [&](const float4 x, f32x4 (&acc)[4]) {
         const float b[4] = {x.x, x.y, x.z, x.w};
 #pragma unroll
@@ -473,18 +553,14 @@ __global__ __launch_bounds__(512) void strip_bwdw_kernel(SWArgs a, ConvArgs f) {
       // every load of this phase unconditional (clamped addresses): a branch join before the image DMA below
       // would make the compiler drain vmcnt before the front
       float4 mA[4], xA;
-      load_mask(a.g2, rb, R, lg4, l16, mA);
-      xA = ld_dpar_raw(rb + l16);
-      float4 qv;
-      {
-        int64_t r = s0 + (tidv & (ST_WIN - 1));
-        r = r < 0 ? 0 : (r >= R ? R - 1 : r);
-        qv = *reinterpret_cast<const float4*>(a.q + r * 4);  // ld4(K) = 4; rows of threads < ST_WIN
-      }
+      ldw(a.g2, mA);
+      xA = ld_dpar_raw();
+      // q row tid (ld4(K) = 4; rows of threads < ST_WIN)
+      const float4 qv = ld_so<float4>(a.q + s0 * 4, 16 * clampw(tid & (ST_WIN - 1)));
       asm volatile("" ::: "memory");
       if (it == a.prof_it) stamp<PROF>(10);
       f32x4 acc[4];
-      front(dpar_mask(rb + l16, xA), acc);
+      front(dpar_mask(xA), acc);
       if constexpr (PROF > 0) {
         if (it == a.prof_it) {
           asm volatile("s_nop 0" : : "v"(acc[3][3]));
@@ -496,7 +572,7 @@ __global__ __launch_bounds__(512) void strip_bwdw_kernel(SWArgs a, ConvArgs f) {
 #pragma unroll
       for (int nb = 0; nb < 4; ++nb)
         *reinterpret_cast<float4*>(sh.RG + (16 * wave + l16) * ST_LDW + nb * 16 + 4 * lg4) = m1[nb];
-      if (tidv < ST_WIN) *reinterpret_cast<float4*>(sh.RE + tidv * SW_LDQ) = qv;
+      if (tid < ST_WIN) *reinterpret_cast<float4*>(sh.RE + tid * SW_LDQ) = qv;
     }
     if (it == a.prof_it) stamp<PROF>(12);
     // the dec_conv2 image for P2's dgrad tile (RW is free since B6 of the last strip): issued after P1 consumed
@@ -509,13 +585,9 @@ __global__ __launch_bounds__(512) void strip_bwdw_kernel(SWArgs a, ConvArgs f) {
     // ================= P2: dec_conv2 weight gradient (needs no image: hides the first strip's image DMA), then
     // dec_conv2 dgrad (mask g1) -> dg1 (registers)
     f32x4 mA[4];  // g2 / dpar rows again (L2), for G2 / DP in P3: in flight across this phase
-    {
-      int64_t r = rb + l16;
-      r = r < 0 ? 0 : (r >= R ? R - 1 : r);
 #pragma unroll
-      for (int nb = 0; nb < 4; ++nb) mA[nb] = *reinterpret_cast<const f32x4*>(a.g2 + r * 64 + nb * 16 + 4 * lg4);
-    }
-    const float4 xA = ld_dpar_raw(rb + l16);  // masked when stored (P3)
+    for (int nb = 0; nb < 4; ++nb) mA[nb] = ld_so<f32x4>(a.g2 + s0 * 64, off64, 64 * nb);
+    const float4 xA = ld_dpar_raw();  // masked when stored (P3)
     {  // tiles (ob = wave / 2, cb = 2 (wave % 2) + j, tap): dY = dg2 (slots), X = g1 (G1)
       const float* ya = sh.RS + (wave >> 1) * 16 + l16;
       const float* xb = sh.RG + (wave & 1) * 32 + l16;
@@ -548,7 +620,7 @@ __global__ __launch_bounds__(512) void strip_bwdw_kernel(SWArgs a, ConvArgs f) {
       *reinterpret_cast<f32x4*>(sh.RS + (16 * wave + 1 + l16) * ST_LDW + nb * 16 + 4 * lg4) = d1[nb];
       *reinterpret_cast<f32x4*>(sh.RW + (16 * wave + l16) * ST_LDW + nb * 16 + 4 * lg4) = mA[nb];
     }
-    *reinterpret_cast<float4*>(sh.RW + RW_DP + (16 * wave + l16) * SW_LDD + 4 * lg4) = dpar_mask(rb + l16, xA);
+    *reinterpret_cast<float4*>(sh.RW + RW_DP + (16 * wave + l16) * SW_LDD + 4 * lg4) = dpar_mask(xA);
     // the enc_conv2 image (30 KB) through registers, stored to RG (free since B2) at the end of P4: an LDS DMA
     // would be drained at P4's first LDS read (the compiler cannot tell its destination from P4's operands)
     constexpr int N2 = 3 * 64 * SB_LDE / 4, C2 = N2 / 64;
@@ -556,19 +628,15 @@ __global__ __launch_bounds__(512) void strip_bwdw_kernel(SWArgs a, ConvArgs f) {
     f32x4 e2v[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {  // a fixed count (the last chunk again where a wave has 3: the same bytes)
-      const int c = min(wave + 8 * j, C2 - 1);
-      e2v[j] = *reinterpret_cast<const f32x4*>(a.img_e2 + 4 * (c * 64 + lane));
+      const int c = min(__builtin_amdgcn_readfirstlane(wave) + 8 * j, C2 - 1);
+      e2v[j] = ld_so<f32x4>(a.img_e2 + c * 256, 16 * lane);
     }
     f32x4 qdl[3], h4[2];  // q, dqx, dlx of row rb + l16 and h2e channels 8 lg4 .. + 7 of it (dec1_epi)
-    {
-      int64_t r = rb + l16;
-      r = r < 0 ? 0 : (r >= R ? R - 1 : r);
-      qdl[0] = *reinterpret_cast<const f32x4*>(f.lb_q + r * 4);
-      qdl[1] = *reinterpret_cast<const f32x4*>(f.lb_dqx + r * 4);
-      qdl[2] = *reinterpret_cast<const f32x4*>(f.lb_dlx + r * 4);
+    qdl[0] = ld_so<f32x4>(f.lb_q + s0 * 4, 16 * cw);
+    qdl[1] = ld_so<f32x4>(f.lb_dqx + s0 * 4, 16 * cw);
+    qdl[2] = ld_so<f32x4>(f.lb_dlx + s0 * 4, 16 * cw);
 #pragma unroll
-      for (int j = 0; j < 2; ++j) h4[j] = *reinterpret_cast<const f32x4*>(f.lb_h + r * 32 + 8 * lg4 + 4 * j);
-    }
+    for (int j = 0; j < 2; ++j) h4[j] = ld_so<f32x4>(f.lb_h + s0 * 32, 128 * cw + 32 * lg4, 16 * j);
     lds_barrier_dma();  // B3: D1, G2, DP, TW (the enc_conv2 image DMA stays in flight: waited in P5)
     if (it == a.prof_it) stamp<PROF>(3);
     // ================= P4: composed dec_conv1 dgrad + softmax backward + to_logits dgrad (dh2 -> Dh2, dlog -> DL);
@@ -576,12 +644,15 @@ __global__ __launch_bounds__(512) void strip_bwdw_kernel(SWArgs a, ConvArgs f) {
     f32x4 h2v[2];  // h2e rows for P5, in flight across this phase
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-      const int i = tidv + 512 * j, row = i >> 3;
-      int64_t r = s0 + row;
-      r = r < 0 ? 0 : (r >= R ? R - 1 : r);
-      h2v[j] = *reinterpret_cast<const f32x4*>(a.h2e + r * 32 + (i & 7) * 4);
+      const int i = tid + 512 * j;  // thread = (window row i / 8, float4 i % 8 of the 32-channel row)
+      h2v[j] = ld_so<f32x4>(a.h2e + s0 * 32, 128 * clampw(i >> 3) + 16 * (i & 7));
     }
-    {
+    // h1e rows (H1 in P5, enc_conv2 dgrad's mask in P6), issued here so that they are a whole phase old at P5:
+    // loaded after the passes, the compiler sank them to just ahead of B4 and P5 opened with their round trip
+    float4 m2[4];
+    ldw(a.h1e, m2);
+    asm volatile("" ::: "memory");
+    {  // (the epilogue ahead of the passes: behind them P4 measured 0.1 us longer)
       f32x4 acc1 = f32x4{0.f, 0.f, 0.f, 0.f};
       c2_tile_n4(sh.RC, sh.RS + 16 * wave * ST_LDW, lg4, l16, acc1);
       dec1_epi(acc1, fsc, rb + l16, R, T, lg4, l16, lsc, qdl, h4, sh.TW, sh.RD + (16 * wave + 1) * SB_LDE,
@@ -601,8 +672,6 @@ __global__ __launch_bounds__(512) void strip_bwdw_kernel(SWArgs a, ConvArgs f) {
                         16 * ST_LDW, 16 * SW_LDQ, [&](ldsp p, int j) { return p[4 * j * ST_LDW]; },
                         [&](ldsp p, int j, int) { return p[4 * j * SW_LDQ]; }, qok, accS0, bS0);
     }
-    float4 m2[4];  // h1e rows: H1 in P5, enc_conv2 dgrad's mask in P6
-    load_mask(a.h1e, rb, R, lg4, l16, m2);
 #pragma unroll
     for (int j = 0; j < 4; ++j) *reinterpret_cast<f32x4*>(sh.RG + min(wave + 8 * j, C2 - 1) * 256 + 4 * lane) = e2v[j];
     lds_barrier_dma();  // B4: D1, G2, DP, Q are read; Dh2, DL and the enc_conv2 image written
@@ -613,20 +682,16 @@ __global__ __launch_bounds__(512) void strip_bwdw_kernel(SWArgs a, ConvArgs f) {
       *reinterpret_cast<float4*>(sh.RW + (16 * wave + l16) * ST_LDW + nb * 16 + 4 * lg4) = m2[nb];
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-      const int i = tidv + 512 * j;
+      const int i = tid + 512 * j;
       *reinterpret_cast<f32x4*>(sh.RS + (i >> 3) * SB_LDE + (i & 7) * 4) = h2v[j];
     }
     lds_barrier();  // B5
     if (it == a.prof_it) stamp<PROF>(5);
     // ================= P6: enc_conv2 dgrad (mask h1) -> dh1 (registers); the enc_conv2 and to_logits (waves 0-1)
     // weight gradients
-    const int xsh = ld4(D) == 8 ? 1 : 0;
-    float4 xv = make_float4(0.f, 0.f, 0.f, 0.f);  // x rows for P7: thread = (row, float4 of the ld4(D) <= 8 row)
-    if (tidv < (ST_WIN << xsh)) {
-      int64_t r = s0 + (tidv >> xsh);
-      r = r < 0 ? 0 : (r >= R ? R - 1 : r);
-      xv = *reinterpret_cast<const float4*>(a.xp + (r << (2 + xsh)) + (tidv & xsh) * 4);
-    }
+    // x rows for P7: thread = (row, float4 of the ld4(D) <= 8 row); threads past the window load its last row
+    // again (not stored)
+    const float4 xv = ld_so<float4>(a.xp + (s0 << (2 + xsh)), (clampw(tid >> xsh) << (4 + xsh)) + 16 * (tid & xsh));
     f32x4 y[4];
     {
       f32x4 acc[4][1];
@@ -640,16 +705,21 @@ __global__ __launch_bounds__(512) void strip_bwdw_kernel(SWArgs a, ConvArgs f) {
     {  // tiles (ob = wave % 2, cb = wave / 2, tap): dY = dh2 (Dh2), X = h1e (H1)
       const float* ya = sh.RD + SB_LDE + (wave & 1) * 16 + l16;
       const float* xb = sh.RW + (wave >> 1) * 16 + l16;
-      wg_pass<3, SEL_NONE>(nstep, to_lds(ya + row0 * SB_LDE), to_lds(xb + (row0 - 1) * ST_LDW), 16 * SB_LDE, 16 * ST_LDW,
-                           [&](ldsp p, int j) { return p[4 * j * SB_LDE]; },
-                           [&](ldsp p, int j, int t) { return p[(4 * j + t) * ST_LDW]; }, true, accE2, bE2);
-    }
-    if (wave < 2) {  // to_logits: tile (0, cb = wave), 1x1: dY = dlog (DL, channels < K), X = h2e (H2)
-      const float* ya = sh.RW + RW_DL + min(l16, 3);
-      const float* xb = sh.RS + wave * 16 + l16;
-      wg_pass<1, SEL_A>(nstep, to_lds(ya + row0 * SW_LDQ), to_lds(xb + row0 * SB_LDE), 16 * SW_LDQ, 16 * SB_LDE,
-                        [&](ldsp p, int j) { return p[4 * j * SW_LDQ]; },
-                        [&](ldsp p, int j, int) { return p[4 * j * SB_LDE]; }, l16 < K, accS1, bS1);
+      auto fa = [&](ldsp p, int j) { return p[4 * j * SB_LDE]; };
+      auto fb = [&](ldsp p, int j, int t) { return p[(4 * j + t) * ST_LDW]; };
+      // on waves 0-1 to_logits' tile rides in the same steps (a pass of its own after this one was a 29-step
+      // dependent chain on two waves, the other six waiting at B6)
+      if (wave < 2) {  // + to_logits: tile (0, cb = wave), 1x1: dY = dlog (DL, channels < K), X = h2e (H2)
+        const float* yc = sh.RW + RW_DL + min(l16, 3);
+        const float* xd = sh.RS + wave * 16 + l16;
+        wg_pass_x<3>(nstep, to_lds(ya + row0 * SB_LDE), to_lds(xb + (row0 - 1) * ST_LDW), 16 * SB_LDE, 16 * ST_LDW, fa, fb,
+                     accE2, bE2, to_lds(yc + row0 * SW_LDQ), to_lds(xd + row0 * SB_LDE), 16 * SW_LDQ, 16 * SB_LDE,
+                     [&](ldsp p, int j) { return p[4 * j * SW_LDQ]; }, [&](ldsp p, int j) { return p[4 * j * SB_LDE]; },
+                     l16 < K, accS1[0], bS1);
+      } else {
+        wg_pass<3, SEL_NONE>(nstep, to_lds(ya + row0 * SB_LDE), to_lds(xb + (row0 - 1) * ST_LDW), 16 * SB_LDE,
+                             16 * ST_LDW, fa, fb, true, accE2, bE2);
+      }
     }
     lds_barrier();  // B6: H1, H2, DL, Dh2 and the enc_conv2 image are read
     if (it == a.prof_it) stamp<PROF>(6);
@@ -657,7 +727,7 @@ __global__ __launch_bounds__(512) void strip_bwdw_kernel(SWArgs a, ConvArgs f) {
 #pragma unroll
     for (int nb = 0; nb < 4; ++nb)
       *reinterpret_cast<f32x4*>(sh.RS + (16 * wave + l16) * ST_LDW + nb * 16 + 4 * lg4) = y[nb];
-    if (tidv < (ST_WIN << xsh)) *reinterpret_cast<float4*>(sh.RD + (tidv >> xsh) * SW_LDQ + (tidv & xsh) * 4) = xv;
+    if (tid < (ST_WIN << xsh)) *reinterpret_cast<float4*>(sh.RD + (tid >> xsh) * SW_LDQ + (tid & xsh) * 4) = xv;
     if (last) {  // after the loop: decoder.conv1's weight (64, 64, 3) for the dE share (LDS DMA, 48 chunks of 1 KB),
       // the share's dWc buffer zeroed (RG: the enc_conv2 image is read)
 #pragma unroll
@@ -665,7 +735,7 @@ __global__ __launch_bounds__(512) void strip_bwdw_kernel(SWArgs a, ConvArgs f) {
         const int c = __builtin_amdgcn_readfirstlane(wave) + 8 * j;
         dma16_uncounted(a.cmpW + c * 256, 16 * lane, sh.RW + c * 256);
       }
-      for (int i = tidv; i < 1536; i += 512) sh.RG[i] = 0.f;
+      for (int i = tid; i < 1536; i += 512) sh.RG[i] = 0.f;
     }
     lds_barrier_dma();  // B7 (the next strip's image DMA stays in flight: waited before B1)
     // ================= P8: enc_conv1 weight gradient (waves 4-7): tile (ob = wave - 4, packed taps): dY = dh1
