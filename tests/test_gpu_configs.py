@@ -53,6 +53,31 @@ def poison_workspace(st, B, T):
     return ws
 
 
+def check_state_vs_oracle(sd, x, u, L, beta, st, rtol_norm=2e-6):
+    """check_step_vs_oracle's `masks` and `grads` rules for a TrainState that has just run forward_backward on the
+    batch (x, u, L: CPU tensors) with the KL weight beta, from the parameters sd (a CPU state dict: the state's
+    parameters BEFORE the step, so an Adam update in the same launch does not matter).  Returns the device's
+    ReLU patterns and the fp64 parameters, whose .grad is the oracle's gradient on the device's branch."""
+    import vqhmm
+    B, _, T = x.shape
+    K, U = st.dims.K, st.dims.u_dim
+    masks = relu_masks(st, B, T)
+    p64 = {k: v.double().requires_grad_(True) for k, v in sd.items()}
+    for name, mk, pre in zip(("enc conv1", "enc conv2", "dec conv1", "dec conv2"), masks,
+                             RM.preactivations({k: v.detach() for k, v in p64.items()}, x.double())):
+        diff = mk != (pre > 0)
+        nd = int(diff.sum())
+        assert nd <= max(4, int(1e-6 * pre.numel())), f"{name}: {nd} ReLU decisions differ from the oracle's"
+        if nd:
+            worst = pre[diff].abs().max().item() / max(pre.abs().max().item(), 1e-30)
+            assert worst <= 1e-4, f"{name}: a flipped ReLU decision at |pre| = {worst:.2e} of the layer max"
+    RM.elbo(p64, x.double(), u.double(), L, beta, K, U, relu_masks=masks).backward()
+    for i, name in enumerate(vqhmm.PARAM_ORDER):
+        g = st.grad[st.off[i]:st.off[i + 1]].view_as(p64[name])
+        assert_grad_close(g.cpu().numpy(), p64[name].grad.numpy(), name, rtol_norm=rtol_norm, rtol_max=10 * rtol_norm)
+    return masks, p64
+
+
 def check_step_vs_oracle(dims, B, T, seed, full_frac=0.5, rtol_norm=2e-6, independent=False, lengths=None,
                          poison=False):
     """The training step (loss + 18 grads) at (B, T) vs the oracle:
@@ -101,16 +126,7 @@ def check_step_vs_oracle(dims, B, T, seed, full_frac=0.5, rtol_norm=2e-6, indepe
         st.check_status()
     assert abs(st.loss.item() - ref_loss) <= LOSS_RTOL * abs(ref_loss), (st.loss.item(), ref_loss)
     assert st.loss.item() == loss.item()
-    masks = relu_masks(st, B, T)
-    p64 = {k: v.double().requires_grad_(True) for k, v in sd.items()}
-    for name, mk, pre in zip(("enc conv1", "enc conv2", "dec conv1", "dec conv2"), masks,
-                             RM.preactivations({k: v.detach() for k, v in p64.items()}, x.double())):
-        diff = mk != (pre > 0)
-        nd = int(diff.sum())
-        assert nd <= max(4, int(1e-6 * pre.numel())), f"{name}: {nd} ReLU decisions differ from the oracle's"
-        if nd:
-            worst = pre[diff].abs().max().item() / max(pre.abs().max().item(), 1e-30)
-            assert worst <= 1e-4, f"{name}: a flipped ReLU decision at |pre| = {worst:.2e} of the layer max"
+    masks, p64 = check_state_vs_oracle(sd, x, u, L, 1.0, st, rtol_norm=rtol_norm)
     rtol_ind = 1e-5
     if independent:  # the fp32 oracle's own ReLU decisions against the device's
         nflip = 0
@@ -121,11 +137,9 @@ def check_step_vs_oracle(dims, B, T, seed, full_frac=0.5, rtol_norm=2e-6, indepe
             nflip += nd
             assert nd <= max(4, int(1e-6 * pre.numel())), f"{name}: {nd} ReLU decisions differ from the fp32 oracle's"
         rtol_ind = 1e-5 if nflip == 0 else 5e-5
-    RM.elbo(p64, x.double(), u.double(), L, 1.0, K, U, relu_masks=masks).backward()
     for i, name in enumerate(vqhmm.PARAM_ORDER):
         g = st.grad[st.off[i]:st.off[i + 1]].view_as(auto[name])
         assert torch.equal(g, auto[name]), name
-        assert_grad_close(g.cpu().numpy(), p64[name].grad.numpy(), name, rtol_norm=rtol_norm, rtol_max=10 * rtol_norm)
         if independent:
             assert_grad_close(g.cpu().numpy(), p32[name].grad.numpy(), name + " (fp32 oracle, own branch)",
                               rtol_norm=rtol_ind, rtol_max=1.0)
