@@ -53,29 +53,46 @@ def poison_workspace(st, B, T):
     return ws
 
 
-def check_state_vs_oracle(sd, x, u, L, beta, st, rtol_norm=2e-6):
-    """check_step_vs_oracle's `masks` and `grads` rules for a TrainState that has just run forward_backward on the
-    batch (x, u, L: CPU tensors) with the KL weight beta, from the parameters sd (a CPU state dict: the state's
-    parameters BEFORE the step, so an Adam update in the same launch does not matter).  Returns the device's
-    ReLU patterns and the fp64 parameters, whose .grad is the oracle's gradient on the device's branch."""
-    import vqhmm
-    B, _, T = x.shape
-    K, U = st.dims.K, st.dims.u_dim
-    masks = relu_masks(st, B, T)
-    p64 = {k: v.double().requires_grad_(True) for k, v in sd.items()}
+def check_masks_vs_oracle(sd, x, masks):
+    """check_step_vs_oracle's `masks` rule: a step's ReLU patterns (relu_masks' CF bool tensors, on the host)
+    against the fp64 oracle's own decisions at the parameters sd (a CPU state dict)."""
     for name, mk, pre in zip(("enc conv1", "enc conv2", "dec conv1", "dec conv2"), masks,
-                             RM.preactivations({k: v.detach() for k, v in p64.items()}, x.double())):
+                             RM.preactivations({k: v.detach().double() for k, v in sd.items()}, x.double())):
         diff = mk != (pre > 0)
         nd = int(diff.sum())
         assert nd <= max(4, int(1e-6 * pre.numel())), f"{name}: {nd} ReLU decisions differ from the oracle's"
         if nd:
             worst = pre[diff].abs().max().item() / max(pre.abs().max().item(), 1e-30)
             assert worst <= 1e-4, f"{name}: a flipped ReLU decision at |pre| = {worst:.2e} of the layer max"
+
+
+def check_masks_grads_vs_oracle(sd, x, u, L, beta, K, U, masks, grad, rtol_norm=2e-6):
+    """check_step_vs_oracle's `masks` and `grads` rules for a step's ReLU patterns `masks` (relu_masks' CF bool
+    tensors) and flat gradient `grad` (vqhmm_param_layout order: the 18 tensors of PARAM_ORDER back to back), on
+    the device or the host, e.g. as a child process saved them.  sd, x, u, L: CPU.  Returns the fp64 parameters,
+    whose .grad is the oracle's gradient on the given branch."""
+    import vqhmm
+    p64 = {k: v.double().requires_grad_(True) for k, v in sd.items()}
+    sizes = [p64[name].numel() for name in vqhmm.PARAM_ORDER]
+    assert grad.numel() == sum(sizes)
+    check_masks_vs_oracle(sd, x, masks)
     RM.elbo(p64, x.double(), u.double(), L, beta, K, U, relu_masks=masks).backward()
-    for i, name in enumerate(vqhmm.PARAM_ORDER):
-        g = st.grad[st.off[i]:st.off[i + 1]].view_as(p64[name])
-        assert_grad_close(g.cpu().numpy(), p64[name].grad.numpy(), name, rtol_norm=rtol_norm, rtol_max=10 * rtol_norm)
-    return masks, p64
+    for name, g in zip(vqhmm.PARAM_ORDER, grad.split(sizes)):
+        assert_grad_close(g.view_as(p64[name]).cpu().numpy(), p64[name].grad.numpy(), name, rtol_norm=rtol_norm,
+                          rtol_max=10 * rtol_norm)
+    return p64
+
+
+def check_state_vs_oracle(sd, x, u, L, beta, st, rtol_norm=2e-6):
+    """check_masks_grads_vs_oracle for a TrainState that has just run forward_backward on the batch (x, u, L: CPU
+    tensors) with the KL weight beta, from the parameters sd (a CPU state dict: the state's parameters BEFORE
+    the step, so an Adam update in the same launch does not matter).  Returns the device's ReLU patterns and the
+    fp64 parameters, whose .grad is the oracle's gradient on the device's branch."""
+    B, _, T = x.shape
+    masks = relu_masks(st, B, T)
+    assert st.off[-1] == st.grad.numel()
+    return masks, check_masks_grads_vs_oracle(sd, x, u, L, beta, st.dims.K, st.dims.u_dim, masks, st.grad,
+                                              rtol_norm=rtol_norm)
 
 
 def check_step_vs_oracle(dims, B, T, seed, full_frac=0.5, rtol_norm=2e-6, independent=False, lengths=None,
