@@ -631,6 +631,79 @@ int vqhmm_gauss_scenario_f32(const float* start, const float* log_A, const float
                              int32_t* states, float* x, float* wealth,
                              float* final_wealth, float* drawdown, void* stream);
 
+/* ------------------- Historical back-test: wealth and its statistics over windows x policies ----
+ * vqhmm_backtest_f32 (hmm_backtest.hip): a regime-conditional portfolio run through B historical windows
+ * under P policies, with rebalancing and transaction costs, in one launch.  returns (B,T,D) fp32; probs
+ * (B,T,S) fp32, any per-step regime distribution (a filter's, a smoother's, an encoder's), not
+ * renormalised; lengths (B) int64, nullable (= T; clamped to [0, T]); weights (P,S,D) fp32; rebalance (P)
+ * int32 >= 1 (a value below 1 is read as 1); tx_cost (P) fp32 >= 0; lag >= 0; hard 0 / 1.  1 <= S <= 32,
+ * 1 <= D <= 64, B, T, P >= 0; T <= 2^28, P <= 2^24, B*P < 2^31 (else VQHMM_EUNSUPPORTED).  Every
+ * arithmetic step from the fp32 inputs is fp64; the order of sums and products is not specified.
+ *
+ * Per window b and policy p, with L the length, R = rebalance[p], c = tx_cost[p], W = weights[p]:
+ *   V = 1, peak = 1, dd = 0, held = 0 (a D-vector), i = -1
+ *   for t = 0 .. L-1:
+ *     tau = 0
+ *     if t >= lag and (t - lag) % R == 0:
+ *       q = probs[b, t - lag]
+ *       target = sum_s q[s] W[s,:]            (hard = 0)
+ *              = W[argmax_s q[s], :]          (hard = 1; the lowest index among equal maxima)
+ *       tau = sum_d |target_d - held_d|;  held = target
+ *     g   = sum_d held_d returns[b,t,d]
+ *     rho = (1 - c tau) (1 + g) - 1           (the step's net return)
+ *     V   = V (1 + rho)
+ *     if V > peak: peak = V, i = t
+ *     if V < peak and 1 - V/peak > dd: dd = 1 - V/peak, i* = i, j* = t
+ * Before step `lag` nothing is held and rho = 0 exactly; lag = 0 trades step t on a row that saw step t.
+ * No clamp where c tau >= 1.  An equal later drawdown does not replace an earlier one.
+ *
+ * stats (B,P,12) fp64, columns: final (V after step L-1), n (= L), sum (of rho), sumsq (of rho^2), n_neg
+ * (steps with rho < 0), sum_neg, sumsq_neg (over those steps), n_pos (steps with rho > 0), drawdown (dd >=
+ * 0), turnover (sum of tau), t_peak (i*), t_trough (j*; both -1 when dd = 0).  L = 0: final 1, the rest 0
+ * and -1, -1.  A non-finite value of returns[b, t, :] or probs[b, t, :] at any t < L makes all twelve
+ * columns of window b NaN for every policy.  wealth (B,P,T) fp32, nullable: V after step t rounded once,
+ * 0 at t >= L; wealth[b,p,L-1] has the bits of (float) final; NaN at t < L in a failed window.
+ *
+ * stats[b,p] and wealth[b,p] are functions of window b's inputs up to its length and of policy p's weights,
+ * rebalance and tx_cost alone: a call on a slice of the windows or of the policies, a call with or without
+ * wealth, and a call with another T beyond the lengths return the same bits.
+ *
+ * vqhmm_backtest_bwd_f32: grad_weights (P,S,D) fp64 = dLoss/dweights given grad_stats (B,P,12) fp64 =
+ * dLoss/dstats, by recomputing the forward pass (nothing is saved).  The columns n, n_neg, n_pos, t_peak,
+ * t_trough carry no gradient; returns and probs receive none.  With g_x the incoming gradient of column x,
+ * the adjoint of step t's net return is
+ *   a_t = g_sum + 2 rho_t g_sumsq + [rho_t < 0] (g_sum_neg + 2 rho_t g_sumsq_neg)
+ *         + g_final V_L / (1 + rho_t) - g_drawdown [i* < t <= j*] (V_j* / V_i*) / (1 + rho_t)     (V_-1 = 1)
+ * and with u_k = g_turnover - c (1 + g_k) a_k at rebalance date k, h_k the holdings taken there (0 before
+ * the first date, sign(0) = 0), the adjoint of h_k is
+ *   abar_k = sum_{t in k's holding period} a_t (1 - c tau_t) returns[b,t,:]
+ *            + u_k sign(h_k - h_{k-1}) - u_{k+1} sign(h_{k+1} - h_k)
+ * and grad_weights[p,s,:] = sum over windows and dates of q_k[s] abar_k (hard = 1: abar_k is added to row
+ * argmax q_k).  The sum over windows is deterministic: fp64 partials per tile of 8 windows in the workspace
+ * (vqhmm_backtest_bwd_workspace_size bytes), added in tile order by a second launch; two identical calls
+ * return identical bits, and a call on a slice of the policies returns the full call's rows.  A failed
+ * window contributes NaN.  grad_weights is written, not accumulated into (B = 0: zeros).
+ *
+ * No host sync, graph-capturable, 64-bit offsets, every global access inside its own array.  Return codes,
+ * checked in this order on the host before any launch: a negative size (B, T, S, D, P, lag) ->
+ * VQHMM_EINVAL; S, D or the sizes out of range -> VQHMM_EUNSUPPORTED (the workspace query returns 0); B*P
+ * == 0 -> VQHMM_OK without a launch (the backward entry with B = 0 < P zeroes grad_weights); a null
+ * required pointer (stats / grad_weights, weights, rebalance, tx_cost; returns and probs when T > 0;
+ * grad_stats and workspace when B > 0) -> VQHMM_EINVAL.  The values of rebalance and tx_cost are device
+ * data and are not checked. */
+int vqhmm_backtest_f32(const float* returns, const float* probs, const int64_t* lengths,
+                       const float* weights, const int32_t* rebalance, const float* tx_cost,
+                       int64_t lag, int hard,
+                       int64_t B, int64_t T, int64_t S, int64_t D, int64_t P,
+                       double* stats, float* wealth, void* stream);
+size_t vqhmm_backtest_bwd_workspace_size(int64_t B, int64_t T, int64_t S, int64_t D, int64_t P);
+int vqhmm_backtest_bwd_f32(const float* returns, const float* probs, const int64_t* lengths,
+                           const float* weights, const int32_t* rebalance, const float* tx_cost,
+                           int64_t lag, int hard,
+                           int64_t B, int64_t T, int64_t S, int64_t D, int64_t P,
+                           const double* grad_stats, double* grad_weights,
+                           void* workspace, void* stream);
+
 /* -------------------------------------------------- codebook learning ----
  * Per-code statistics of a batch under given assignments, the quantizer's backward from the same
  * pass, and the channels-first lookup (pseudocode.txt:8-32, the codebook's side; vq_codebook.hip).

@@ -51,6 +51,12 @@
                                                         (the codebook statistics / the quantizer's fused backward;
                                                          --old-route: also bincount + index_add_ / the torch backward
                                                          of vqhmm.quantize, in five alternating pairs)
+    python tools/kbench.py backtest --B 512 --T 252 --K 3 --D 12 --P 64 [--hard] [--bwd] [--old-route]
+                                                        (vqhmm.backtest: B windows x P weight tables, S = K regimes;
+                                                         --bwd: with an objective on metrics() and its backward;
+                                                         --old-route: also the torch fp64 restatement (einsum, gather,
+                                                         cumprod, cummax; autograd with --bwd), five alternating pairs,
+                                                         a check line on stats and gradient within the derived bound)
 """
 import argparse
 import json
@@ -998,6 +1004,156 @@ def bench_gauss_scenario(a):
         print(json.dumps(rec))
 
 
+def bench_backtest(a):
+    """vqhmm.backtest (vqhmm_backtest_f32; with --bwd also an objective on Backtest.metrics() and its backward,
+    vqhmm_backtest_bwd_f32) at --B windows x --T steps, S = --K regimes, --D assets, --P weight tables, rebalance 5,
+    tx_cost 1e-3, lag 1, full lengths; --hard: mode="hard".  --old-route: also the straightforward torch fp64
+    restatement: H = einsum(probs[:, dates - lag], W), a gather of H to the steps, (held r).sum(-1), the dates'
+    diff().abs().sum(-1), cumprod, cummax and the sums (a (B,P,T,D) fp64 intermediate), with --bwd torch autograd
+    through it; five alternating pairs after a warm-up.  The check line compares the two routes' stats (and with
+    --bwd the gradients of the objective) against tol = 4 (T + S + D + B + 8) 2^-53 mag, mag the sum of the
+    absolute values of the terms that enter each output (tests/backtest_ref.py's rule, evaluated in torch)."""
+    B, T, S, D, P = a.B, a.T, a.K, a.D, a.P
+    R, cost, lag = 5, 1e-3, 1
+    g = torch.Generator(device="cuda").manual_seed(21)
+    r = (1e-3 + 1e-2 * torch.randn((B, T, D), device="cuda", generator=g)).contiguous()
+    logit = torch.randn((B, T, S), device="cuda", generator=g).cumsum(1) * 0.5
+    probs = torch.softmax(logit - logit.mean(2, keepdim=True), 2).contiguous()
+    W0 = torch.rand((P, S, D), device="cuda", generator=g) + 0.1
+    W0 = (W0 / W0.sum(2, keepdim=True)).contiguous()
+    reb = torch.full((P,), R, dtype=torch.int32, device="cuda")
+    txc = torch.full((P,), cost, dtype=torch.float32, device="cuda")
+    c64 = float(txc[0].double())
+    mode = "hard" if a.hard else "soft"
+    tt = torch.arange(T, device="cuda")
+    dates = torch.arange(lag, T, R, device="cuda")
+    kidx = ((tt - lag).clamp_min(0) // R)
+    live = (tt >= lag).double()[:, None]
+    r64 = r.double()
+
+    def rows():
+        q = probs[:, dates - lag].double()
+        if a.hard:
+            q = torch.nn.functional.one_hot(q.argmax(2), S).double()
+        return q
+
+    def old_stats(W):
+        q = rows()                                                   # (B,K,S)
+        H = torch.einsum("bks,psd->bpkd", q, W.double())
+        held = H[:, :, kidx] * live                                  # (B,P,T,D)
+        gr = (held * r64[:, None]).sum(-1)
+        tauk = torch.cat([H[:, :, :1], H.diff(dim=2)], 2).abs().sum(-1)
+        tau = torch.zeros_like(gr).index_copy(2, dates, tauk)
+        rho = (1.0 - c64 * tau) * (1.0 + gr) - 1.0
+        V = torch.cumprod(1.0 + rho, -1)
+        cm = torch.cummax(V, -1)
+        peak = cm.values.clamp_min(1.0)
+        dds = 1.0 - V / peak
+        dd, jt = dds.max(-1)
+        it = torch.where(cm.values.gather(2, jt[..., None])[..., 0] > 1.0, cm.indices.gather(2, jt[..., None])[..., 0],
+                         torch.full_like(jt, -1))
+        none = dd <= 0
+        neg = rho < 0
+        rn = torch.where(neg, rho, torch.zeros_like(rho))
+        n = torch.full_like(dd, float(T))
+        cols = [V[..., -1], n, rho.sum(-1), (rho * rho).sum(-1), neg.sum(-1).double(), rn.sum(-1), (rn * rn).sum(-1),
+                (rho > 0).sum(-1).double(), dd, tau.sum(-1), torch.where(none, -torch.ones_like(dd), it.double()),
+                torch.where(none, -torch.ones_like(dd), jt.double())]
+        return torch.stack(cols, -1), (rho, gr, tau, q)
+
+    def objective(stats):
+        m = vqhmm.Backtest(stats).metrics()
+        return (-m["sharpe"] + 0.1 * stats[..., 8] + 0.01 * stats[..., 9] - torch.log(stats[..., 0])
+                + m["sortino"]).sum()
+
+    def new_fwd():
+        return vqhmm.backtest(r, probs, W0, rebalance=reb, tx_cost=txc, lag=lag, mode=mode).stats
+
+    def old_fwd():
+        with torch.no_grad():
+            return old_stats(W0)[0]
+
+    def new_bwd():
+        W = W0.clone().requires_grad_(True)
+        objective(vqhmm.backtest(r, probs, W, rebalance=reb, tx_cost=txc, lag=lag, mode=mode).stats).backward()
+        return W.grad
+
+    def old_bwd():
+        W = W0.clone().requires_grad_(True)
+        objective(old_stats(W)[0]).backward()
+        return W.grad
+
+    name = "backtest_bwd" if a.bwd else "backtest"
+    legs = {name: new_bwd if a.bwd else new_fwd}
+    dims = {"B": B, "T": T, "S": S, "D": D, "P": P, "mode": mode}
+    if a.old_route:
+        legs["old_route"] = old_bwd if a.bwd else old_fwd
+        k = 4.0 * (T + S + D + B + 8) * 2.0 ** -53
+        with torch.no_grad():
+            so, (rho, gr, tau, q) = old_stats(W0)
+            sn = new_fwd()
+            Wa = W0.double().abs()
+            Ha = torch.einsum("bks,psd->bpkd", q.abs(), Wa)
+            gabs = (Ha[:, :, kidx] * live * r64[:, None].abs()).sum(-1)
+            tabk = (Ha + torch.cat([torch.zeros_like(Ha[:, :, :1]), Ha[:, :, :-1]], 2)).sum(-1)
+            tabs = torch.zeros_like(gr).index_copy(2, dates, tabk)
+            terms = (1.0 + c64 * tabs) * (1.0 + gabs)
+            rel = terms / (1.0 + rho).abs()
+            rt = terms + 1.0
+            sq = 2.0 * rho.abs() * rt + rho * rho
+            neg = rho < 0
+            inside = (tt > so[..., 10, None]) & (tt <= so[..., 11, None])
+            zero = torch.zeros_like(rt)
+            mag = {0: so[..., 0].abs() * rel.sum(-1), 2: rt.sum(-1), 3: sq.sum(-1), 5: torch.where(neg, rt, zero).sum(-1),
+                   6: torch.where(neg, sq, zero).sum(-1), 9: tabs.sum(-1),
+                   8: 1.0 + (1.0 - so[..., 8]) * (1.0 + torch.where(inside, rel, zero).sum(-1))}
+            chk = {"int_columns_equal": bool(all(torch.equal(so[..., c], sn[..., c]) for c in (1, 4, 7, 10, 11)))}
+            worst = 0.0
+            for c, m in mag.items():
+                worst = max(worst, ((so[..., c] - sn[..., c]).abs() / (k * m)).max().item())
+            chk["stats_err_over_tol"] = worst
+        if a.bwd:
+            W = W0.clone().double().requires_grad_(True)
+            bt = vqhmm.backtest(r, probs, W, rebalance=reb, tx_cost=txc, lag=lag, mode=mode)
+            bt.stats.retain_grad()
+            objective(bt.stats).backward()
+            gs = bt.stats.grad
+            Wo = W0.clone().double().requires_grad_(True)
+            objective(old_stats(Wo)[0]).backward()
+            with torch.no_grad():
+                ins = inside.double()
+                A = (gs[..., 2, None].abs() + 2 * rho.abs() * gs[..., 3, None].abs()
+                     + neg * (gs[..., 5, None].abs() + 2 * rho.abs() * gs[..., 6, None].abs())
+                     + (gs[..., 0, None] * so[..., 0, None]).abs() / (1 + rho).abs()
+                     + ins * (gs[..., 8, None].abs() * (1 - so[..., 8, None])) / (1 + rho).abs())
+                qs = q[:, kidx] * live[None]                                      # (B,T,S)
+                m1 = torch.einsum("bpt,bts,btd->psd", A * (1 - c64 * tau).abs() * live[:, 0], qs.abs(), r64.abs())
+                dq = torch.cat([q[:, :1], q.diff(dim=1)], 1).abs()                 # (B,K,S)
+                uab = gs[..., 9, None].abs() + c64 * (1 + gr.abs()[:, :, dates]) * A[:, :, dates]
+                m2 = torch.einsum("bpk,bks->ps", uab, dq)[..., None]
+                err = (W.grad - Wo.grad).abs()
+                chk["grad_err_over_tol"] = (err / (k * (m1 + m2))).max().item()
+                chk["grad_max_rel"] = (err.max() / Wo.grad.abs().max()).item()
+            del bt, gs, A, qs, m1, m2, W, Wo
+        chk["agree"] = bool(chk["int_columns_equal"] and chk["stats_err_over_tol"] <= 1.0
+                            and chk.get("grad_err_over_tol", 0.0) <= 1.0)
+        print(json.dumps(dict({"check": "old_route vs " + name}, **dims, **chk)))
+        del so, sn, rho, gr, tau, q, Ha, gabs, tabs, terms, rel, rt, sq, mag
+        torch.cuda.empty_cache()
+    rounds = _pairs(legs)
+    t = {k_: sorted(v)[len(v) // 2] for k_, v in rounds.items()}
+    for k_ in legs:
+        rec = dict({"kernel": k_}, **dims, us=t[k_] * 1e6, min_us=min(rounds[k_]) * 1e6, max_us=max(rounds[k_]) * 1e6,
+                   pairs_us=[x * 1e6 for x in rounds[k_]])
+        if k_ == "old_route":
+            rec["x_" + name] = t[k_] / t[name]
+            rec["fused_not_slower_in_any_pair"] = all(o >= f for o, f in zip(rounds[k_], rounds[name]))
+        else:
+            byts = 4 * B * T * (D + S) + 96 * B * P
+            rec.update(GBps=byts / t[k_] / 1e9, frac_hbm=byts / t[k_] / HBM_PEAK)
+        print(json.dumps(rec))
+
+
 def torch_ffbs(filt, log_A, u):
     """Plain-torch FFBS on full-length sequences, one step per iteration: a gather of the column
     z_t, a cumsum and a searchsorted (several launches per time step)."""
@@ -1086,6 +1242,9 @@ if __name__ == "__main__":
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--old-route", action="store_true")
     ap.add_argument("--full", action="store_true")
+    ap.add_argument("--P", type=int, default=8)
+    ap.add_argument("--hard", action="store_true")
+    ap.add_argument("--bwd", action="store_true")
     a = ap.parse_args()
     {"vq": bench_vq, "stream": bench_stream, "viterbi": bench_viterbi, "fwdbwd": bench_fwdbwd,
      "filter": bench_filter, "xi": bench_xi, "estep": bench_estep, "estep_batched": bench_estep_batched,
@@ -1094,4 +1253,4 @@ if __name__ == "__main__":
      "gauss_moments": bench_gauss_moments, "code_fit": bench_code_fit, "code_viterbi": bench_code_viterbi,
      "code_filter": bench_code_filter, "gauss_viterbi": bench_gauss_viterbi, "gauss_filter": bench_gauss_filter,
      "sample": bench_sample, "vq_stats": bench_vq_stats, "gauss_scenario": bench_gauss_scenario,
-     "vq_bwd": bench_vq_bwd}[a.what](a)
+     "vq_bwd": bench_vq_bwd, "backtest": bench_backtest}[a.what](a)

@@ -655,6 +655,36 @@ int vqhmm_gauss_scenario_f32(const float* start, const float* log_A, const float
                                    S, D, states, x, wealth, final_wealth, drawdown, (hipStream_t)stream);
 }
 
+int vqhmm_backtest_f32(const float* returns, const float* probs, const int64_t* lengths, const float* weights,
+                       const int32_t* rebalance, const float* tx_cost, int64_t lag, int hard, int64_t B, int64_t T,
+                       int64_t S, int64_t D, int64_t P, double* stats, float* wealth, void* stream) {
+  if (B < 0 || T < 0 || S < 0 || D < 0 || P < 0 || lag < 0) return VQHMM_EINVAL;
+  if (!hmm_backtest_supported(B, T, S, D, P)) return VQHMM_EUNSUPPORTED;
+  if (B == 0 || P == 0) return VQHMM_OK;
+  if (!stats || !weights || !rebalance || !tx_cost) return VQHMM_EINVAL;
+  if (T > 0 && (!returns || !probs)) return VQHMM_EINVAL;
+  return launch_hmm_backtest(returns, probs, lengths, weights, rebalance, tx_cost, lag, hard, B, T, S, D, P, stats,
+                             wealth, (hipStream_t)stream);
+}
+
+size_t vqhmm_backtest_bwd_workspace_size(int64_t B, int64_t T, int64_t S, int64_t D, int64_t P) {
+  return hmm_backtest_bwd_ws_bytes(B, T, S, D, P);
+}
+
+int vqhmm_backtest_bwd_f32(const float* returns, const float* probs, const int64_t* lengths, const float* weights,
+                           const int32_t* rebalance, const float* tx_cost, int64_t lag, int hard, int64_t B,
+                           int64_t T, int64_t S, int64_t D, int64_t P, const double* grad_stats,
+                           double* grad_weights, void* workspace, void* stream) {
+  if (B < 0 || T < 0 || S < 0 || D < 0 || P < 0 || lag < 0) return VQHMM_EINVAL;
+  if (!hmm_backtest_supported(B, T, S, D, P)) return VQHMM_EUNSUPPORTED;
+  if (P == 0) return VQHMM_OK;
+  if (!grad_weights || !weights || !rebalance || !tx_cost) return VQHMM_EINVAL;
+  if (B > 0 && (!grad_stats || !workspace)) return VQHMM_EINVAL;
+  if (B > 0 && T > 0 && (!returns || !probs)) return VQHMM_EINVAL;
+  return launch_hmm_backtest_bwd(returns, probs, lengths, weights, rebalance, tx_cost, lag, hard, B, T, S, D, P,
+                                 grad_stats, grad_weights, workspace, (hipStream_t)stream);
+}
+
 size_t vqhmm_vq_stats_workspace_size(int64_t B, int64_t Dv, int64_t T, int64_t K) {
   return vq_codebook_ws_bytes(B, Dv, T, K);
 }

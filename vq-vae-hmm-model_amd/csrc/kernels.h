@@ -605,6 +605,18 @@ int launch_hmm_gauss_scenario(const float* start, const float* log_A, const floa
                               const float* port, int64_t rebalance, float tx_cost, uint64_t seed, int64_t b0,
                               int64_t n0, int64_t B, int64_t N, int64_t H, int64_t S, int64_t D, int32_t* states,
                               float* x, float* wealth, float* final_wealth, float* drawdown, hipStream_t s);
+// historical back-test (hmm_backtest.hip): B windows x P policies, stats (B,P,12) fp64 and the nullable wealth
+// (B,P,T) in one launch without a workspace; the backward pass recomputes the forward one and leaves
+// grad_weights (P,S,D) fp64 = the fixed-order sum of per-tile partials (ws = hmm_backtest_bwd_ws_bytes)
+bool hmm_backtest_supported(int64_t B, int64_t T, int64_t S, int64_t D, int64_t P);
+size_t hmm_backtest_bwd_ws_bytes(int64_t B, int64_t T, int64_t S, int64_t D, int64_t P);
+int launch_hmm_backtest(const float* returns, const float* probs, const int64_t* lengths, const float* weights,
+                        const int32_t* rebalance, const float* tx_cost, int64_t lag, int hard, int64_t B, int64_t T,
+                        int64_t S, int64_t D, int64_t P, double* stats, float* wealth, hipStream_t s);
+int launch_hmm_backtest_bwd(const float* returns, const float* probs, const int64_t* lengths, const float* weights,
+                            const int32_t* rebalance, const float* tx_cost, int64_t lag, int hard, int64_t B,
+                            int64_t T, int64_t S, int64_t D, int64_t P, const double* grad_stats,
+                            double* grad_weights, void* ws, hipStream_t s);
 // codebook learning (vq_codebook.hip), 1 <= K <= 65536, 1 <= Dv <= 512, K Dv <= 2^21: per-code count / residual
 // sum / sse in fp64 under given assignments (each nullable here), and with dz the quantizer's backward from the
 // same pass (dz = g_zq + *dz_scale r, dcb = *dcb_scale rsum from the reduce launch); ws = vq_codebook_ws_bytes.

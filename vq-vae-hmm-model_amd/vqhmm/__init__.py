@@ -15,6 +15,7 @@ import os as _os
 _os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")
 
 from . import _ext  # noqa: E402,F401
+from .backtest import Backtest, backtest  # noqa: E402,F401
 from .checkpoint import load_checkpoint, load_encoder, save_checkpoint, save_encoder  # noqa: E402,F401
 from .codebook import Codebook  # noqa: E402,F401
 from .codehmm import CodeHMM, code_log_prob  # noqa: E402,F401
@@ -35,4 +36,4 @@ __all__ = ["VAE_HMM", "Encoder", "Prior", "Decoder", "train_model", "Trainer", "
            "save_checkpoint", "load_checkpoint", "save_encoder", "load_encoder", "infer", "hard_regimes", "viterbi_regimes",
            "prior_viterbi", "forward_filter", "pairwise_posteriors", "filtered_regimes", "CodeHMM", "CodeHMMEnsemble", "code_log_prob", "Codebook", "GaussianHMM", "gauss_log_prob",
            "gauss_full_log_prob", "regime_moments", "regime_covariance", "GaussianHMMEnsemble", "Scenarios", "scenario_summary",
-           "sample_posterior_paths", "simulate_paths", "sampled_regimes", "simulate_regimes"]
+           "sample_posterior_paths", "simulate_paths", "sampled_regimes", "simulate_regimes", "backtest", "Backtest"]

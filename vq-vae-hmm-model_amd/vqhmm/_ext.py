@@ -101,6 +101,11 @@ _SIGS = {
     "vqhmm_gauss_scenario_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.c_int, c_vp, c_i64, c_f32,
                                                 ctypes.c_uint64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64,
                                                 c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "vqhmm_backtest_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, ctypes.c_int, c_i64, c_i64, c_i64,
+                                          c_i64, c_i64, c_vp, c_vp, c_vp]),
+    "vqhmm_backtest_bwd_workspace_size": (c_sz, [c_i64, c_i64, c_i64, c_i64, c_i64]),
+    "vqhmm_backtest_bwd_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, ctypes.c_int, c_i64, c_i64,
+                                              c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "vqhmm_vq_stats_workspace_size": (c_sz, [c_i64, c_i64, c_i64, c_i64]),
     "vqhmm_vq_stats_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp,
                                           c_sz, c_vp]),

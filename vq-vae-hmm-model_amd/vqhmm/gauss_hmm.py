@@ -516,6 +516,18 @@ class GaussianHMM(torch.nn.Module):
                        "GaussianHMM.decode")
         return path, score
 
+    def backtest(self, x, returns, weights, lengths=None, causal=True, **kw):
+        """Label the history with this model and run `weights` through it: vqhmm.backtest(returns, probs, weights,
+        lengths, **kw) with probs = filter(x, lengths)[0] (causal=True: step t's row has seen x up to t only) or
+        posterior(x, lengths) (causal=False: the smoother, which has seen the whole window, for attribution rather
+        than for a tradable result).  x (B,T,dim) are the model's observations, returns (B,T,D) the assets' step
+        returns; they may be the same tensor.  The equal-weight buy-and-hold benchmark is weights = 1 / D in every
+        row with tx_cost = 0.  -> Backtest."""
+        from .backtest import backtest
+        with torch.no_grad():
+            probs = self.filter(x, lengths)[0] if causal else self.posterior(x, lengths)
+        return backtest(returns, probs, weights, lengths=lengths, **kw)
+
     def _filter(self, x, lengths, state, want_filt):
         x, lengths, B, T = self._inputs(x, lengths)
         S, D = self.num_states, self.dim
