@@ -93,7 +93,8 @@ int vqhmm_vq_argmin_f32(const float* z, int64_t B, int64_t Dv, int64_t T,
  * the argmin kernel's epilogue where its row-load path runs (Dv in {4,8,16,32,64}, T % 4 == 0,
  * K <= 32), else argmin + one gather launch; then one fixed-order partial-sum launch (the result
  * is deterministic).  Replaces the reference's `quantize` + two MSEs.
- * Workspace: vqhmm_vq_quantize_workspace_size(B, Dv, T, K) bytes. */
+ * Workspace: vqhmm_vq_quantize_workspace_size(B, Dv, T, K) bytes.
+ * B * T == 0: VQHMM_OK, *sse = 0 (the empty sum) and nothing else is written. */
 size_t vqhmm_vq_quantize_workspace_size(int64_t B, int64_t Dv, int64_t T, int64_t K);
 int vqhmm_vq_quantize_f32(const float* z, int64_t B, int64_t Dv, int64_t T, const float* codebook, int64_t K,
                           int32_t* idx, float* z_q_st, double* sse, void* workspace, size_t ws_bytes,
@@ -114,7 +115,8 @@ int vqhmm_vq_quantize_f32(const float* z, int64_t B, int64_t Dv, int64_t T, cons
  * aligned.
  * Workspace: vqhmm_viterbi_workspace_size(B, T, K) bytes (backpointers as one
  * 64-bit lane ballot per step per wave of 64 / KP^2 sequences, KP = K rounded
- * up to a power of two; T rounded up to 64). */
+ * up to a power of two; T rounded up to 64).
+ * T = 0 (or B = 0) returns VQHMM_OK without a launch and writes nothing, score included. */
 size_t vqhmm_viterbi_workspace_size(int64_t B, int64_t T, int64_t K);
 int vqhmm_viterbi_f32(const float* log_pi, const float* log_A, const float* em, const int64_t* lengths,
                       int64_t B, int64_t T, int64_t K, int32_t* path, float* score, void* workspace,
@@ -134,7 +136,8 @@ int vqhmm_viterbi_f32(const float* log_pi, const float* log_A, const float* em, 
  * log_pi, log_A and em need only 4-byte alignment: every kernel variant then meets the same
  * accuracy target (K = 4 and K = 8 stage the tables in 16-step instead of 32-step chunks, so the
  * bits may differ from an aligned call's within it); gamma, logZ and the workspace must be 16-byte
- * aligned (the parallel-in-time kernel stores K = 8 gamma rows as 16-byte vectors). */
+ * aligned (the parallel-in-time kernel stores K = 8 gamma rows as 16-byte vectors).
+ * T = 0 (or B = 0) returns VQHMM_OK without a launch and writes nothing, logZ included. */
 size_t vqhmm_fwdbwd_workspace_size(int64_t B, int64_t T, int64_t K);
 int vqhmm_fwdbwd_f32(const float* log_pi, const float* log_A, const float* em, const int64_t* lengths,
                      int64_t B, int64_t T, int64_t K, float* gamma, float* logZ, void* workspace,
@@ -161,7 +164,8 @@ int vqhmm_fwdbwd_f32(const float* log_pi, const float* log_A, const float* em, c
  * d logZ / d em = gamma, d logZ / d log_pi = sum_b gamma[b,0].
  * Workspace: vqhmm_fwdbwd_xi_workspace_size(B, T, K) bytes (0 if K is unsupported).
  * Accuracy target vs the fp64 oracle: |xi| abs 2e-5.
- * Neither kernel reads outside [0, B*T*K*K) of log_A or [0, B*T*K) of em / gamma. */
+ * Neither kernel reads outside [0, B*T*K*K) of log_A or [0, B*T*K) of em / gamma.
+ * T = 0 (or B = 0) returns VQHMM_OK without a launch and writes nothing, loglik / logZ included. */
 int vqhmm_filter_f32(const float* log_pi, const float* log_A, const float* em, const int64_t* lengths,
                      int64_t B, int64_t T, int64_t K, float* filt, float* loglik, void* stream);
 size_t vqhmm_fwdbwd_xi_workspace_size(int64_t B, int64_t T, int64_t K);

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import backtest_ref as BR
+from gpu_buffers import check_all, guarded
 
 pytestmark = pytest.mark.gpu
 
@@ -37,21 +38,22 @@ def dev(a):
 
 
 def run_fwd(c, lag, hard, want_wealth=True):
-    """Through ctypes on exact-size buffers pre-filled with 7 -> (stats, wealth or None) as numpy."""
+    """Through ctypes on guarded exact-size buffers (gpu_buffers.guarded) pre-filled with 7 -> (stats, wealth or
+    None) as numpy."""
     from vqhmm import _ext
     lib = _ext.load()
     B, T, D = c["returns"].shape
     S, P = c["probs"].shape[2], c["weights"].shape[0]
     d = {k: dev(c[k]) for k in ("returns", "probs", "weights", "rebalance", "tx_cost")}
     lengths = dev(c["lengths"]) if c.get("lengths") is not None else None
-    stats = torch.full((B, P, 12), 7.0, dtype=torch.float64, device="cuda")
-    wealth = torch.full((B, P, T), 7.0, dtype=torch.float32, device="cuda") if want_wealth else None
+    stats = guarded((B, P, 12), torch.float64, fill=7.0)
+    wealth = guarded((B, P, T), torch.float32, fill=7.0) if want_wealth else None
     rc = lib.vqhmm_backtest_f32(_ext.ptr(d["returns"]), _ext.ptr(d["probs"]), _ext.ptr(lengths), _ext.ptr(d["weights"]),
                                 _ext.ptr(d["rebalance"]), _ext.ptr(d["tx_cost"]), lag, hard, B, T, S, D, P,
-                                _ext.ptr(stats), _ext.ptr(wealth), _ext.stream_ptr())
+                                stats.ptr, wealth.ptr if want_wealth else None, _ext.stream_ptr())
     assert rc == 0, rc
-    torch.cuda.synchronize()
-    return stats.cpu().numpy(), (wealth.cpu().numpy() if want_wealth else None)
+    check_all(stats, wealth)
+    return stats.t.cpu().numpy(), (wealth.t.cpu().numpy() if want_wealth else None)
 
 
 def run_bwd(c, lag, hard, gstats):
@@ -62,15 +64,15 @@ def run_bwd(c, lag, hard, gstats):
     d = {k: dev(c[k]) for k in ("returns", "probs", "weights", "rebalance", "tx_cost")}
     lengths = dev(c["lengths"]) if c.get("lengths") is not None else None
     g = dev(np.asarray(gstats, np.float64))
-    grad = torch.full((P, S, D), 7.0, dtype=torch.float64, device="cuda")
+    grad = guarded((P, S, D), torch.float64, fill=7.0)
     nb = lib.vqhmm_backtest_bwd_workspace_size(B, T, S, D, P)
-    ws = torch.full((max(nb, 1),), 7, dtype=torch.uint8, device="cuda")
+    ws = guarded(nb, torch.uint8)  # exactly the queried size, poisoned
     rc = lib.vqhmm_backtest_bwd_f32(_ext.ptr(d["returns"]), _ext.ptr(d["probs"]), _ext.ptr(lengths),
                                     _ext.ptr(d["weights"]), _ext.ptr(d["rebalance"]), _ext.ptr(d["tx_cost"]), lag, hard,
-                                    B, T, S, D, P, _ext.ptr(g), _ext.ptr(grad), _ext.ptr(ws), _ext.stream_ptr())
+                                    B, T, S, D, P, _ext.ptr(g), grad.ptr, ws.ptr, _ext.stream_ptr())
     assert rc == 0, rc
-    torch.cuda.synchronize()
-    return grad.cpu().numpy()
+    check_all(grad, ws)
+    return grad.t.cpu().numpy()
 
 
 def check_fwd(got_stats, got_wealth, f, what):

@@ -15,6 +15,7 @@ import torch
 
 import code_decode_ref as D
 import code_hmm_ref as R
+from gpu_buffers import check_all, guarded
 
 pytestmark = pytest.mark.gpu
 NINF = -np.inf
@@ -40,9 +41,11 @@ def dev(a, dtype, offset=False):
 
 
 def out(shape, dtype, offset=False, fill=7):
-    n = int(np.prod(shape))
-    buf = torch.full((n + (1 if offset else 0),), fill, dtype=dtype, device="cuda")
-    return (buf[1:] if offset else buf).view(shape)
+    """A guarded exact-size output (gpu_buffers.guarded) filled with `fill`; offset: 4 bytes past a 16-byte
+    boundary, the guards around that view."""
+    g = guarded(shape, dtype, fill=fill, offset=offset)
+    assert g.t.data_ptr() % 16 == (4 if offset else 0) or g.nbytes == 0
+    return g
 
 
 def raw_viterbi(model, codes, lengths, offset=False):
@@ -57,13 +60,13 @@ def raw_viterbi(model, codes, lengths, offset=False):
     path = out((B, T), torch.int32, offset)
     score = out((B,), torch.float32, offset)
     nb = lib.vqhmm_code_viterbi_workspace_size(B, T, S, V)
-    ws = torch.empty(max(nb, 1), dtype=torch.uint8, device="cuda")
+    ws = guarded(nb, torch.uint8)  # exactly the queried size, poisoned
     rc = lib.vqhmm_code_viterbi_f32(_ext.ptr(log_pi), _ext.ptr(log_A), _ext.ptr(log_B), _ext.ptr(d_codes),
-                                    _ext.ptr(d_len), B, T, S, V, _ext.ptr(path), _ext.ptr(score), _ext.ptr(ws), nb,
+                                    _ext.ptr(d_len), B, T, S, V, path.ptr, score.ptr, ws.ptr, nb,
                                     _ext.stream_ptr())
     assert rc == 0, rc
-    torch.cuda.synchronize()
-    return path.cpu().numpy(), score.cpu().numpy()
+    check_all(path, score, ws)
+    return path.t.cpu().numpy(), score.t.cpu().numpy()
 
 
 def raw_filter(model, codes, lengths, prev=None, offset=False, want_filt=True, no_pi=False):
@@ -80,13 +83,14 @@ def raw_filter(model, codes, lengths, prev=None, offset=False, want_filt=True, n
     last = out((B, S), torch.float32, offset)
     ll = out((B,), torch.float32, offset)
     nb = lib.vqhmm_code_filter_workspace_size(B, T, S, V)
-    ws = torch.empty(max(nb, 1), dtype=torch.uint8, device="cuda")
+    ws = guarded(nb, torch.uint8)  # exactly the queried size, poisoned
     rc = lib.vqhmm_code_filter_f32(_ext.ptr(None if no_pi else log_pi), _ext.ptr(log_A), _ext.ptr(log_B),
-                                   _ext.ptr(d_codes), _ext.ptr(d_len), _ext.ptr(d_prev), B, T, S, V, _ext.ptr(filt),
-                                   _ext.ptr(last), _ext.ptr(ll), _ext.ptr(ws), nb, _ext.stream_ptr())
+                                   _ext.ptr(d_codes), _ext.ptr(d_len), _ext.ptr(d_prev), B, T, S, V,
+                                   None if filt is None else filt.ptr, last.ptr, ll.ptr, ws.ptr, nb, _ext.stream_ptr())
     assert rc == 0, rc
-    torch.cuda.synchronize()
-    return dict(filt=None if filt is None else filt.cpu().numpy(), last=last.cpu().numpy(), loglik=ll.cpu().numpy())
+    check_all(filt, last, ll, ws)
+    return dict(filt=None if filt is None else filt.t.cpu().numpy(), last=last.t.cpu().numpy(),
+                loglik=ll.t.cpu().numpy())
 
 
 def bits(a):
@@ -341,9 +345,8 @@ def test_return_codes_and_empty_shapes():
     codes = torch.zeros((B, 6), dtype=torch.int32, device="cuda")
     lens = torch.full((B,), 6, dtype=torch.int64, device="cuda")
     ws = torch.empty(1 << 16, dtype=torch.uint8, device="cuda")
-    score = out((B,), torch.float32)
-    path = out((B, 6), torch.int32)
-    last, ll = out((B, S), torch.float32), out((B,), torch.float32)
+    g_out = [out((B,), torch.float32), out((B, 6), torch.int32), out((B, S), torch.float32), out((B,), torch.float32)]
+    score, path, last, ll = (g.t for g in g_out)
     prev = torch.rand((B, S), device="cuda")
 
     def vit(B_=B, T=6, S_=S, V_=V, lp=d[0], w=ws, nb=1 << 16):
@@ -374,6 +377,7 @@ def test_return_codes_and_empty_shapes():
     assert fil(lp=None, pv=prev) == 0
     torch.cuda.synchronize()
     assert torch.isfinite(ll).all()
+    check_all(*g_out)
 
 
 # ------------------------------------------------------------------------------ CodeHMM

@@ -16,6 +16,7 @@ import torch
 import code_ens_ref as E
 import code_hmm_ref as R
 import test_gpu_code_hmm as G
+from gpu_buffers import check_all, guarded
 
 pytestmark = pytest.mark.gpu
 NINF = -np.inf
@@ -33,8 +34,9 @@ def stack(models):
 
 
 def raw_batched(models, codes, lengths, weights=None, loglik=True, gamma=True, offset=False, M=None):
-    """vqhmm_code_estep_batched_f32 through ctypes on exact-size buffers; the counts start as NaN and loglik /
-    gamma as 7 (the call must write every element) -> (rc, dict of device tensors)."""
+    """vqhmm_code_estep_batched_f32 through ctypes on guarded exact-size buffers and a guarded, poisoned
+    workspace of exactly the queried size (gpu_buffers.guarded); the counts start as NaN and loglik / gamma as 7
+    (the call must write every element) -> (rc, dict of device tensors)."""
     from vqhmm import _ext
     lib = _ext.load()
     log_pi, log_A, log_B = (G.dev_f32(a, offset) for a in stack(models))
@@ -44,17 +46,18 @@ def raw_batched(models, codes, lengths, weights=None, loglik=True, gamma=True, o
     d_codes = G.dev_i32(codes, offset) if codes.size else torch.zeros(1, dtype=torch.int32, device="cuda")
     d_len = torch.from_numpy(np.asarray(lengths, np.int64)).cuda()
     d_w = None if weights is None else G.dev_f32(weights, offset)
-    cnt = [torch.full(sh, float("nan"), dtype=torch.float64, device="cuda") for sh in ((Mm, S), (Mm, S, S), (Mm, S, V))]
-    ll = torch.full((Mm, B), 7.0, dtype=torch.float32, device="cuda") if loglik else None
-    gm = torch.full((Mm, B, T, S), 7.0, dtype=torch.float32, device="cuda") if gamma else None
+    cnt = [guarded(sh, torch.float64, fill=float("nan")) for sh in ((Mm, S), (Mm, S, S), (Mm, S, V))]
+    ll = guarded((Mm, B), torch.float32, fill=7.0) if loglik else None
+    gm = guarded((Mm, B, T, S), torch.float32, fill=7.0) if gamma else None
     nb = lib.vqhmm_code_estep_batched_workspace_size(B, T, S, V, M)
-    ws = torch.empty(max(nb, 1), dtype=torch.uint8, device="cuda")
+    ws = guarded(nb, torch.uint8)
     rc = lib.vqhmm_code_estep_batched_f32(_ext.ptr(log_pi), _ext.ptr(log_A), _ext.ptr(log_B), _ext.ptr(d_codes),
-                                          _ext.ptr(d_len), _ext.ptr(d_w), B, T, S, V, M, _ext.ptr(cnt[0]),
-                                          _ext.ptr(cnt[1]), _ext.ptr(cnt[2]), _ext.ptr(ll), _ext.ptr(gm), _ext.ptr(ws),
+                                          _ext.ptr(d_len), _ext.ptr(d_w), B, T, S, V, M, cnt[0].ptr, cnt[1].ptr,
+                                          cnt[2].ptr, ll.ptr if loglik else None, gm.ptr if gamma else None, ws.ptr,
                                           nb, _ext.stream_ptr())
-    torch.cuda.synchronize()
-    return rc, dict(pi_cnt=cnt[0], trans_cnt=cnt[1], emit_cnt=cnt[2], loglik=ll, gamma=gm)
+    check_all(*cnt, ll, gm, ws)
+    return rc, dict(pi_cnt=cnt[0].t, trans_cnt=cnt[1].t, emit_cnt=cnt[2].t, loglik=ll.t if loglik else None,
+                    gamma=gm.t if gamma else None)
 
 
 def make_members(seed, M, S, V, B, T, scale=1.5):

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import code_hmm_ref as R
+from gpu_buffers import check_all, guarded
 
 pytestmark = pytest.mark.gpu
 NINF = -np.inf
@@ -47,8 +48,9 @@ def dev_i32(a, offset=False):
 
 
 def raw_estep(model, codes, lengths, loglik=True, gamma=True, offset=False):
-    """vqhmm_code_estep_f32 through ctypes on exact-size buffers; the counts start as NaN (the call must
-    write every element) -> dict of device tensors."""
+    """vqhmm_code_estep_f32 through ctypes on guarded exact-size buffers (gpu_buffers.guarded) and a
+    guarded, poisoned workspace of exactly the queried size; the counts start as NaN (the call must write
+    every element) -> dict of device tensors."""
     from vqhmm import _ext
     lib = _ext.load()
     log_pi, log_A, log_B = (dev_f32(a, offset) for a in model)
@@ -56,17 +58,18 @@ def raw_estep(model, codes, lengths, loglik=True, gamma=True, offset=False):
     B, T = codes.shape
     d_codes = dev_i32(codes, offset)
     d_len = torch.from_numpy(np.asarray(lengths, np.int64)).cuda()
-    cnt = [torch.full(sh, float("nan"), dtype=torch.float64, device="cuda") for sh in ((S,), (S, S), (S, V))]
-    ll = torch.full((B,), 7.0, dtype=torch.float32, device="cuda") if loglik else None
-    gm = torch.full((B, T, S), 7.0, dtype=torch.float32, device="cuda") if gamma else None
+    cnt = [guarded(sh, torch.float64, fill=float("nan")) for sh in ((S,), (S, S), (S, V))]
+    ll = guarded((B,), torch.float32, fill=7.0) if loglik else None
+    gm = guarded((B, T, S), torch.float32, fill=7.0) if gamma else None
     nb = lib.vqhmm_code_estep_workspace_size(B, T, S, V)
-    ws = torch.empty(max(nb, 1), dtype=torch.uint8, device="cuda")
+    ws = guarded(nb, torch.uint8)
     rc = lib.vqhmm_code_estep_f32(_ext.ptr(log_pi), _ext.ptr(log_A), _ext.ptr(log_B), _ext.ptr(d_codes),
-                                  _ext.ptr(d_len), B, T, S, V, _ext.ptr(cnt[0]), _ext.ptr(cnt[1]), _ext.ptr(cnt[2]),
-                                  _ext.ptr(ll), _ext.ptr(gm), _ext.ptr(ws), nb, _ext.stream_ptr())
+                                  _ext.ptr(d_len), B, T, S, V, cnt[0].ptr, cnt[1].ptr, cnt[2].ptr,
+                                  ll.ptr if loglik else None, gm.ptr if gamma else None, ws.ptr, nb, _ext.stream_ptr())
     assert rc == 0, rc
-    torch.cuda.synchronize()
-    return dict(pi_cnt=cnt[0], trans_cnt=cnt[1], emit_cnt=cnt[2], loglik=ll, gamma=gm)
+    check_all(*cnt, ll, gm, ws)
+    return dict(pi_cnt=cnt[0].t, trans_cnt=cnt[1].t, emit_cnt=cnt[2].t, loglik=ll.t if loglik else None,
+                gamma=gm.t if gamma else None)
 
 
 def rel_ok(got, ref, tol=1e-5):
@@ -411,13 +414,13 @@ def raw_sample(model, u):
     S, V = log_B.shape
     N, T = u.shape[:2]
     d_u = dev_f32(u)
-    st = torch.full((N, T), -7, dtype=torch.int32, device="cuda")
-    cd = torch.full((N, T), -7, dtype=torch.int32, device="cuda")
+    st = guarded((N, T), torch.int32, fill=-7)
+    cd = guarded((N, T), torch.int32, fill=-7)
     rc = lib.vqhmm_code_sample_f32(_ext.ptr(log_pi), _ext.ptr(log_A), _ext.ptr(log_B), _ext.ptr(d_u), N, T, S, V,
-                                   _ext.ptr(st), _ext.ptr(cd), _ext.stream_ptr())
+                                   st.ptr, cd.ptr, _ext.stream_ptr())
     assert rc == 0, rc
-    torch.cuda.synchronize()
-    return st.cpu().numpy(), cd.cpu().numpy()
+    check_all(st, cd)
+    return st.t.cpu().numpy(), cd.t.cpu().numpy()
 
 
 @pytest.mark.parametrize("S,V,seed", R.SAMPLER_CASES)

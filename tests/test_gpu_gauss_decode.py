@@ -17,6 +17,7 @@ import torch
 import gauss_decode_ref as D
 import gauss_full_ref as GF
 import gauss_hmm_ref as G
+from gpu_buffers import check_all, guarded
 
 pytestmark = pytest.mark.gpu
 NINF = -np.inf
@@ -44,9 +45,11 @@ def dev(a, dtype=np.float32, offset=False):
 
 
 def out(shape, dtype, offset=False, fill=7):
-    n = int(np.prod(shape))
-    buf = torch.full((n + (1 if offset else 0),), fill, dtype=dtype, device="cuda")
-    return (buf[1:] if offset else buf).view(shape)
+    """A guarded exact-size output (gpu_buffers.guarded) filled with `fill`; offset: 4 bytes past a 16-byte
+    boundary, the guards around that view."""
+    g = guarded(shape, dtype, fill=fill, offset=offset)
+    assert g.t.data_ptr() % 16 == (4 if offset else 0) or g.nbytes == 0
+    return g
 
 
 def _lib():
@@ -63,11 +66,11 @@ def raw_emission(full, model, x, lengths):
     d_x, d_len = dev(x), dev(lengths, np.int64)
     em = out((B, T, S), torch.float32)
     entry = lib.vqhmm_gauss_full_emission_f32 if full else lib.vqhmm_gauss_emission_f32
-    rc = entry(_ext.ptr(mean), _ext.ptr(par), _ext.ptr(d_x), _ext.ptr(d_len), B, T, S, Dm, _ext.ptr(em),
+    rc = entry(_ext.ptr(mean), _ext.ptr(par), _ext.ptr(d_x), _ext.ptr(d_len), B, T, S, Dm, em.ptr,
                _ext.stream_ptr())
     assert rc == 0, rc
-    torch.cuda.synchronize()
-    return em.cpu().numpy()
+    check_all(em)
+    return em.t.cpu().numpy()
 
 
 def raw_viterbi(full, model, x, lengths, offset=False):
@@ -82,12 +85,12 @@ def raw_viterbi(full, model, x, lengths, offset=False):
     size, entry = ((lib.vqhmm_gauss_full_viterbi_workspace_size, lib.vqhmm_gauss_full_viterbi_f32) if full
                    else (lib.vqhmm_gauss_viterbi_workspace_size, lib.vqhmm_gauss_viterbi_f32))
     nb = size(B, T, S, Dm)
-    ws = torch.empty(max(nb, 1), dtype=torch.uint8, device="cuda")  # exactly the queried size
+    ws = guarded(nb, torch.uint8)  # exactly the queried size, poisoned
     rc = entry(_ext.ptr(log_pi), _ext.ptr(log_A), _ext.ptr(mean), _ext.ptr(par), _ext.ptr(d_x), _ext.ptr(d_len), B, T,
-               S, Dm, _ext.ptr(path), _ext.ptr(score), _ext.ptr(ws), nb, _ext.stream_ptr())
+               S, Dm, path.ptr, score.ptr, ws.ptr, nb, _ext.stream_ptr())
     assert rc == 0, rc
-    torch.cuda.synchronize()
-    return path.cpu().numpy(), score.cpu().numpy()
+    check_all(path, score, ws)
+    return path.t.cpu().numpy(), score.t.cpu().numpy()
 
 
 def raw_filter(full, model, x, lengths, prev=None, offset=False, want=("filt", "last", "loglik"), no_pi=False):
@@ -103,11 +106,11 @@ def raw_filter(full, model, x, lengths, prev=None, offset=False, want=("filt", "
                 loglik=out((B,), torch.float32, offset) if "loglik" in want else None)
     entry = lib.vqhmm_gauss_full_filter_f32 if full else lib.vqhmm_gauss_filter_f32
     rc = entry(_ext.ptr(None if no_pi else log_pi), _ext.ptr(log_A), _ext.ptr(mean), _ext.ptr(par), _ext.ptr(d_x),
-               _ext.ptr(d_len), _ext.ptr(d_prev), B, T, S, Dm, _ext.ptr(bufs["filt"]), _ext.ptr(bufs["last"]),
-               _ext.ptr(bufs["loglik"]), _ext.stream_ptr())
+               _ext.ptr(d_len), _ext.ptr(d_prev), B, T, S, Dm,
+               *(None if bufs[k] is None else bufs[k].ptr for k in ("filt", "last", "loglik")), _ext.stream_ptr())
     assert rc == 0, rc
-    torch.cuda.synchronize()
-    return {k: None if v is None else v.cpu().numpy() for k, v in bufs.items()}
+    check_all(*bufs.values())
+    return {k: None if v is None else v.t.cpu().numpy() for k, v in bufs.items()}
 
 
 def bits(a):
@@ -495,7 +498,8 @@ def test_empty_shapes(full):
     vit = lib.vqhmm_gauss_full_viterbi_f32 if full else lib.vqhmm_gauss_viterbi_f32
     fil = lib.vqhmm_gauss_full_filter_f32 if full else lib.vqhmm_gauss_filter_f32
     lens = torch.zeros((B,), dtype=torch.int64, device="cuda")
-    score, ll, last = out((B,), torch.float32), out((B,), torch.float32), out((B, S), torch.float32)
+    g_out = [out((B,), torch.float32), out((B,), torch.float32), out((B, S), torch.float32), out((B, 5), torch.int32)]
+    score, ll, last, path = (g.t for g in g_out)
     prev = torch.rand((B, S), device="cuda")
     # (B, T) = (3, 0): every length is 0, the size-B outputs are written, no pointer but theirs is needed
     assert vit(None, None, None, None, None, None, B, 0, S, Dm, None, P(score), None, 0, sp()) == 0
@@ -510,11 +514,11 @@ def test_empty_shapes(full):
     assert fil(*(P(m) for m in model), None, P(lens), None, 0, 5, S, Dm, None, None, None, sp()) == 0
     # T > 0 and every length 0
     x = torch.zeros((B, 5, Dm), device="cuda")
-    path = out((B, 5), torch.int32)
     ws = torch.empty(4096, dtype=torch.uint8, device="cuda")
     assert vit(*(P(m) for m in model), P(x), P(lens), B, 5, S, Dm, P(path), P(score), P(ws), 4096, sp()) == 0
     torch.cuda.synchronize()
     assert (path == -1).all() and (score == NINF).all()
+    check_all(*g_out)
 
 
 # ------------------------------------------------------------------------------ GaussianHMM

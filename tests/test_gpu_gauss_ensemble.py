@@ -17,6 +17,7 @@ import gauss_full_ref as F
 import gauss_hmm_ref as G
 import test_gpu_gauss_full as HF
 import test_gpu_gauss_hmm as H
+from gpu_buffers import check_all, guarded
 
 pytestmark = pytest.mark.gpu
 NINF = -np.inf
@@ -62,8 +63,9 @@ def _entries(full):
 
 def raw_batched(full, models, x, lengths, shift=None, weights=None, loglik=True, gamma=True, offset=False,
                 expect=0):
-    """The batched entry through ctypes on exact-size buffers (offset: every float buffer 4 bytes into its
-    allocation); the counts start as NaN (the call must write every element) -> dict of device tensors."""
+    """The batched entry through ctypes on guarded exact-size outputs and a guarded, poisoned workspace of
+    exactly the queried size (gpu_buffers.guarded; offset: every float input 4 bytes into its allocation); the
+    counts start as NaN (the call must write every element) -> dict of device tensors."""
     from vqhmm import _ext
     size, entry = _entries(full)
     M = len(models)
@@ -74,17 +76,17 @@ def raw_batched(full, models, x, lengths, shift=None, weights=None, loglik=True,
     d_len = torch.from_numpy(np.asarray(lengths, np.int64)).cuda()
     d_sh, d_w = dev_f32(shift, offset), dev_f32(weights, offset)
     shapes = ((M, S), (M, S, S), (M, S), (M, S, D), (M, S, D, D) if full else (M, S, D))
-    cnt = {k: torch.full(sh, float("nan"), dtype=torch.float64, device="cuda") for k, sh in zip(COUNTS, shapes)}
-    ll = torch.full((M, B), 7.0, dtype=torch.float32, device="cuda") if loglik else None
-    gm = torch.full((M, B, T, S), 7.0, dtype=torch.float32, device="cuda") if gamma else None
+    cnt = {k: guarded(sh, torch.float64, fill=float("nan")) for k, sh in zip(COUNTS, shapes)}
+    ll = guarded((M, B), torch.float32, fill=7.0) if loglik else None
+    gm = guarded((M, B, T, S), torch.float32, fill=7.0) if gamma else None
     nb = size(B, T, S, D, M)
-    ws = torch.empty(max(nb, 1), dtype=torch.uint8, device="cuda")
+    ws = guarded(nb, torch.uint8)
     rc = entry(_ext.ptr(log_pi), _ext.ptr(log_A), _ext.ptr(mean), _ext.ptr(last), _ext.ptr(d_x), _ext.ptr(d_len),
-               _ext.ptr(d_sh), _ext.ptr(d_w), B, T, S, D, M, *(_ext.ptr(cnt[k]) for k in COUNTS), _ext.ptr(ll),
-               _ext.ptr(gm), _ext.ptr(ws), nb, _ext.stream_ptr())
+               _ext.ptr(d_sh), _ext.ptr(d_w), B, T, S, D, M, *(cnt[k].ptr for k in COUNTS), ll.ptr if loglik else None,
+               gm.ptr if gamma else None, ws.ptr, nb, _ext.stream_ptr())
     assert rc == expect, rc
-    torch.cuda.synchronize()
-    return dict(cnt, loglik=ll, gamma=gm)
+    check_all(*cnt.values(), ll, gm, ws)
+    return dict({k: g.t for k, g in cnt.items()}, loglik=ll.t if loglik else None, gamma=gm.t if gamma else None)
 
 
 def same_bits(a, b):

@@ -19,6 +19,7 @@ import torch
 
 import gauss_full_ref as F
 import test_gpu_gauss_hmm as H
+from gpu_buffers import check_all, guarded
 
 pytestmark = pytest.mark.gpu
 NINF = -np.inf
@@ -48,16 +49,17 @@ def raw_emission(model, x, lengths, offset=False, fill=7.0):
     B, T = x.shape[:2]
     d_x = dev_f32(x, offset)
     d_len = torch.from_numpy(np.asarray(lengths, np.int64)).cuda()
-    em = torch.full((B, T, S), fill, dtype=torch.float32, device="cuda")
+    em = guarded((B, T, S), torch.float32, fill=fill)
     rc = lib.vqhmm_gauss_full_emission_f32(_ext.ptr(mean), _ext.ptr(W), _ext.ptr(d_x), _ext.ptr(d_len), B, T, S, D,
-                                           _ext.ptr(em), _ext.stream_ptr())
+                                           em.ptr, _ext.stream_ptr())
     assert rc == 0, rc
-    torch.cuda.synchronize()
-    return em
+    check_all(em)
+    return em.t
 
 
 def raw_estep(model, x, lengths, shift=None, weights=None, loglik=True, gamma=True, offset=False):
-    """vqhmm_gauss_full_estep_f32 through ctypes on exact-size buffers; the counts start as NaN (the call must
+    """vqhmm_gauss_full_estep_f32 through ctypes on guarded exact-size buffers and a guarded, poisoned workspace of exactly the
+    queried size (gpu_buffers.guarded); the counts start as NaN (the call must
     write every element) -> dict of device tensors."""
     from vqhmm import _ext
     lib = _ext.load()
@@ -67,23 +69,24 @@ def raw_estep(model, x, lengths, shift=None, weights=None, loglik=True, gamma=Tr
     d_x = dev_f32(x, offset)
     d_len = torch.from_numpy(np.asarray(lengths, np.int64)).cuda()
     d_sh, d_w = dev_f32(shift, offset), dev_f32(weights, offset)
-    cnt = {k: torch.full(sh, float("nan"), dtype=torch.float64, device="cuda")
+    cnt = {k: guarded(sh, torch.float64, fill=float("nan"))
            for k, sh in zip(COUNTS, ((S,), (S, S), (S,), (S, D), (S, D, D)))}
-    ll = torch.full((B,), 7.0, dtype=torch.float32, device="cuda") if loglik else None
-    gm = torch.full((B, T, S), 7.0, dtype=torch.float32, device="cuda") if gamma else None
+    ll = guarded((B,), torch.float32, fill=7.0) if loglik else None
+    gm = guarded((B, T, S), torch.float32, fill=7.0) if gamma else None
     nb = lib.vqhmm_gauss_full_estep_workspace_size(B, T, S, D)
-    ws = torch.empty(max(nb, 1), dtype=torch.uint8, device="cuda")
+    ws = guarded(nb, torch.uint8)  # exactly the queried size, poisoned
     rc = lib.vqhmm_gauss_full_estep_f32(_ext.ptr(log_pi), _ext.ptr(log_A), _ext.ptr(mean), _ext.ptr(W),
                                         _ext.ptr(d_x), _ext.ptr(d_len), _ext.ptr(d_sh), _ext.ptr(d_w), B, T, S, D,
-                                        *(_ext.ptr(cnt[k]) for k in COUNTS), _ext.ptr(ll), _ext.ptr(gm),
-                                        _ext.ptr(ws), nb, _ext.stream_ptr())
+                                        *(cnt[k].ptr for k in COUNTS), ll.ptr if loglik else None, gm.ptr if gamma else None,
+                                        ws.ptr, nb, _ext.stream_ptr())
     assert rc == 0, rc
-    torch.cuda.synchronize()
-    return dict(cnt, loglik=ll, gamma=gm)
+    check_all(*cnt.values(), ll, gm, ws)
+    return dict({k: g.t for k, g in cnt.items()}, loglik=ll.t if loglik else None, gamma=gm.t if gamma else None)
 
 
 def raw_moments(x, gamma, lengths, shift=None, weights=None, offset=False):
-    """vqhmm_gauss_moments_f32 through ctypes on exact-size, NaN-prefilled buffers."""
+    """vqhmm_gauss_moments_f32 through ctypes on guarded exact-size, NaN-prefilled buffers and a guarded, poisoned
+    workspace of exactly the queried size."""
     from vqhmm import _ext
     lib = _ext.load()
     B, T, D = x.shape
@@ -91,16 +94,16 @@ def raw_moments(x, gamma, lengths, shift=None, weights=None, offset=False):
     d_x, d_g = dev_f32(x, offset), dev_f32(gamma, offset)
     d_len = torch.from_numpy(np.asarray(lengths, np.int64)).cuda()
     d_sh, d_w = dev_f32(shift, offset), dev_f32(weights, offset)
-    cnt = {k: torch.full(sh, float("nan"), dtype=torch.float64, device="cuda")
+    cnt = {k: guarded(sh, torch.float64, fill=float("nan"))
            for k, sh in zip(("occ", "m1", "m2"), ((S,), (S, D), (S, D, D)))}
     nb = lib.vqhmm_gauss_moments_workspace_size(B, T, S, D)
-    ws = torch.empty(max(nb, 1), dtype=torch.uint8, device="cuda")
+    ws = guarded(nb, torch.uint8)  # exactly the queried size, poisoned
     rc = lib.vqhmm_gauss_moments_f32(_ext.ptr(d_x), _ext.ptr(d_g), _ext.ptr(d_len), _ext.ptr(d_sh), _ext.ptr(d_w),
-                                     B, T, S, D, *(_ext.ptr(cnt[k]) for k in ("occ", "m1", "m2")), _ext.ptr(ws), nb,
+                                     B, T, S, D, *(cnt[k].ptr for k in ("occ", "m1", "m2")), ws.ptr, nb,
                                      _ext.stream_ptr())
     assert rc == 0, rc
-    torch.cuda.synchronize()
-    return cnt
+    check_all(*cnt.values(), ws)
+    return {k: g.t for k, g in cnt.items()}
 
 
 def count_bounds(loglik, x, lengths, shift, weights):

@@ -18,6 +18,7 @@ import pytest
 import torch
 
 import gauss_hmm_ref as R
+from gpu_buffers import check_all, guarded
 
 pytestmark = pytest.mark.gpu
 NINF = -np.inf
@@ -55,16 +56,17 @@ def raw_emission(model, x, lengths, offset=False, fill=7.0):
     B, T = x.shape[:2]
     d_x = dev_f32(x, offset)
     d_len = torch.from_numpy(np.asarray(lengths, np.int64)).cuda()
-    em = torch.full((B, T, S), fill, dtype=torch.float32, device="cuda")
+    em = guarded((B, T, S), torch.float32, fill=fill)
     rc = lib.vqhmm_gauss_emission_f32(_ext.ptr(mean), _ext.ptr(log_var), _ext.ptr(d_x), _ext.ptr(d_len), B, T, S, D,
-                                      _ext.ptr(em), _ext.stream_ptr())
+                                      em.ptr, _ext.stream_ptr())
     assert rc == 0, rc
-    torch.cuda.synchronize()
-    return em
+    check_all(em)
+    return em.t
 
 
 def raw_estep(model, x, lengths, shift=None, weights=None, loglik=True, gamma=True, offset=False):
-    """vqhmm_gauss_estep_f32 through ctypes on exact-size buffers; the counts start as NaN (the call must write
+    """vqhmm_gauss_estep_f32 through ctypes on guarded exact-size buffers and a guarded, poisoned workspace of exactly the
+    queried size (gpu_buffers.guarded); the counts start as NaN (the call must write
     every element) -> dict of device tensors."""
     from vqhmm import _ext
     lib = _ext.load()
@@ -74,19 +76,19 @@ def raw_estep(model, x, lengths, shift=None, weights=None, loglik=True, gamma=Tr
     d_x = dev_f32(x, offset)
     d_len = torch.from_numpy(np.asarray(lengths, np.int64)).cuda()
     d_sh, d_w = dev_f32(shift, offset), dev_f32(weights, offset)
-    cnt = {k: torch.full(sh, float("nan"), dtype=torch.float64, device="cuda")
+    cnt = {k: guarded(sh, torch.float64, fill=float("nan"))
            for k, sh in zip(COUNTS, ((S,), (S, S), (S,), (S, D), (S, D)))}
-    ll = torch.full((B,), 7.0, dtype=torch.float32, device="cuda") if loglik else None
-    gm = torch.full((B, T, S), 7.0, dtype=torch.float32, device="cuda") if gamma else None
+    ll = guarded((B,), torch.float32, fill=7.0) if loglik else None
+    gm = guarded((B, T, S), torch.float32, fill=7.0) if gamma else None
     nb = lib.vqhmm_gauss_estep_workspace_size(B, T, S, D)
-    ws = torch.empty(max(nb, 1), dtype=torch.uint8, device="cuda")
+    ws = guarded(nb, torch.uint8)  # exactly the queried size, poisoned
     rc = lib.vqhmm_gauss_estep_f32(_ext.ptr(log_pi), _ext.ptr(log_A), _ext.ptr(mean), _ext.ptr(log_var), _ext.ptr(d_x),
                                    _ext.ptr(d_len), _ext.ptr(d_sh), _ext.ptr(d_w), B, T, S, D,
-                                   *(_ext.ptr(cnt[k]) for k in COUNTS), _ext.ptr(ll), _ext.ptr(gm), _ext.ptr(ws), nb,
+                                   *(cnt[k].ptr for k in COUNTS), ll.ptr if loglik else None, gm.ptr if gamma else None, ws.ptr, nb,
                                    _ext.stream_ptr())
     assert rc == 0, rc
-    torch.cuda.synchronize()
-    return dict(cnt, loglik=ll, gamma=gm)
+    check_all(*cnt.values(), ll, gm, ws)
+    return dict({k: g.t for k, g in cnt.items()}, loglik=ll.t if loglik else None, gamma=gm.t if gamma else None)
 
 
 def rel_ok(got, ref, tol=1e-5):

@@ -17,6 +17,7 @@ import torch
 
 import gauss_scenario_ref as R
 from gauss_scenario_ref import EXACT_CASES, case_inputs
+from gpu_buffers import check_all, guarded
 
 pytestmark = pytest.mark.gpu
 SEED = 1234
@@ -30,8 +31,8 @@ def dev(a, dtype=np.float32):
 
 
 def run(c, B, N, H, want=ALL, seed=SEED, b0=0, n0=0, reb=5, tx=1e-3, port=True, start=None, log_A=None, rc=0):
-    """The entry through ctypes on exact-size buffers -> dict of numpy arrays; every requested output starts as 7
-    (the call must write every element)."""
+    """The entry through ctypes on guarded exact-size buffers (gpu_buffers.guarded) -> dict of numpy arrays; every
+    requested output starts as 7 (the call must write every element)."""
     from vqhmm import _ext
     lib = _ext.load()
     S, D = c["mean"].shape
@@ -39,13 +40,14 @@ def run(c, B, N, H, want=ALL, seed=SEED, b0=0, n0=0, reb=5, tx=1e-3, port=True, 
             dev(c["scale"])]
     d_port = dev(c["port"]) if port else None
     shapes = {"states": (B, N, H), "x": (B, N, H, D), "wealth": (B, N, H), "final": (B, N), "drawdown": (B, N)}
-    outs = {k: (torch.full(shapes[k], 7, dtype=torch.int32 if k == "states" else torch.float32, device="cuda")
-                if k in want else None) for k in ALL}
+    outs = {k: (guarded(shapes[k], torch.int32 if k == "states" else torch.float32, fill=7) if k in want else None)
+            for k in ALL}
     got = lib.vqhmm_gauss_scenario_f32(*(_ext.ptr(t) for t in d_in), int(c["full"]), _ext.ptr(d_port), reb, tx, seed,
-                                       b0, n0, B, N, H, S, D, *(_ext.ptr(outs[k]) for k in ALL), _ext.stream_ptr())
+                                       b0, n0, B, N, H, S, D, *(None if outs[k] is None else outs[k].ptr for k in ALL),
+                                       _ext.stream_ptr())
     assert got == rc, got
-    torch.cuda.synchronize()
-    return {k: v.cpu().numpy() for k, v in outs.items() if v is not None}
+    check_all(*outs.values())
+    return {k: v.t.cpu().numpy() for k, v in outs.items() if v is not None}
 
 
 @functools.lru_cache(maxsize=None)

@@ -7,6 +7,7 @@ import pytest
 import torch
 
 import vq_codebook_ref as R
+from gpu_buffers import check_all, guarded
 
 pytestmark = pytest.mark.gpu
 
@@ -40,34 +41,38 @@ def _dev(a):
 
 
 def _stats(z, idx, lengths, cb):
+    """vqhmm_vq_stats_f32 on guarded, NaN-prefilled count / sum / sse buffers and a guarded, poisoned workspace of
+    exactly the queried size (gpu_buffers.guarded) -> the three outputs concatenated."""
     from vqhmm import _ext
     lib = _ext.load()
     B, Dv, T = z.shape
     K = cb.shape[0]
-    flat = torch.full((K + K * Dv + 1,), float("nan"), dtype=torch.float64, device="cuda")
+    outs = [guarded((n,), torch.float64, fill=float("nan")) for n in (K, K * Dv, 1)]
     nb = lib.vqhmm_vq_stats_workspace_size(B, Dv, T, K)
-    ws = torch.empty(nb, dtype=torch.uint8, device="cuda")
+    ws = guarded(nb, torch.uint8)
     _ext.check(lib.vqhmm_vq_stats_f32(_ext.ptr(z), _ext.ptr(idx), _ext.ptr(lengths), B, Dv, T, _ext.ptr(cb), K,
-                                      _ext.ptr(flat[:K]), _ext.ptr(flat[K:K + K * Dv]), _ext.ptr(flat[K + K * Dv:]),
-                                      _ext.ptr(ws), nb, _ext.stream_ptr()), "stats")
-    return flat
+                                      outs[0].ptr, outs[1].ptr, outs[2].ptr, ws.ptr, nb, _ext.stream_ptr()), "stats")
+    check_all(*outs, ws)
+    return torch.cat([g.t for g in outs])
 
 
 def _bwd(z, idx, lengths, cb, g, s, c):
+    """vqhmm_vq_quantize_bwd_f32 on guarded, NaN-prefilled dz / dcodebook and a guarded, poisoned workspace."""
     from vqhmm import _ext
     lib = _ext.load()
     B, Dv, T = z.shape
     K = cb.shape[0]
-    dz = torch.full_like(z, float("nan"))
-    dcb = torch.full_like(cb, float("nan"))
+    dz = guarded(z.shape, torch.float32, fill=float("nan"))
+    dcb = guarded(cb.shape, torch.float32, fill=float("nan"))
     st = torch.tensor([s], dtype=torch.float32, device="cuda")
     ct = torch.tensor([c], dtype=torch.float32, device="cuda")
     nb = lib.vqhmm_vq_quantize_bwd_workspace_size(B, Dv, T, K)
-    ws = torch.empty(nb, dtype=torch.uint8, device="cuda")
+    ws = guarded(nb, torch.uint8)
     _ext.check(lib.vqhmm_vq_quantize_bwd_f32(_ext.ptr(z), _ext.ptr(idx), _ext.ptr(lengths), B, Dv, T, _ext.ptr(cb), K,
-                                             _ext.ptr(g), _ext.ptr(st), _ext.ptr(ct), _ext.ptr(dz), _ext.ptr(dcb),
-                                             _ext.ptr(ws), nb, _ext.stream_ptr()), "bwd")
-    return dz, dcb
+                                             _ext.ptr(g), _ext.ptr(st), _ext.ptr(ct), dz.ptr, dcb.ptr,
+                                             ws.ptr, nb, _ext.stream_ptr()), "bwd")
+    check_all(dz, dcb, ws)
+    return dz.t, dcb.t
 
 
 @pytest.mark.parametrize("mode", MODES)

@@ -527,7 +527,9 @@ size_t vq_quantize_ws_bytes(int64_t B, int64_t Dv, int64_t T, int64_t K) {
 int launch_vq_quantize(const float* z, int64_t B, int64_t Dv, int64_t T, const float* cb, int64_t K, int32_t* idx,
                        float* zq_st, double* sse, void* ws, size_t ws_bytes, hipStream_t s) {
   const int64_t N = B * T;
-  if (K <= 0 || Dv <= 0 || Dv > 2048 || T <= 0 || T > INT32_MAX) return VQHMM_EINVAL;
+  // T = 0 is an empty problem like B = 0 (as vqhmm_vq_argmin_f32 takes it): no argmin or gather launch,
+  // *sse = 0 by the partial-sum launch below
+  if (K <= 0 || Dv <= 0 || Dv > 2048 || T < 0 || T > INT32_MAX) return VQHMM_EINVAL;
   if (ws_bytes < vq_quantize_ws_bytes(B, Dv, T, K)) return VQHMM_EWORKSPACE;
   double* part = reinterpret_cast<double*>(ws);
   int64_t np;

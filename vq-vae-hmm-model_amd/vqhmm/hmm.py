@@ -120,6 +120,13 @@ def _hmm_inputs(log_pi, log_A, em, lengths):
     return (log_pi.contiguous().float(), log_A.contiguous().float(), em.contiguous().float(), lengths, B, T, K)
 
 
+def _length0(B, value, device):
+    """The (B,) result of a batch of length-0 sequences.  For T = 0 the C entries launch nothing and
+    write nothing (include/vqhmm.h), so the wrappers fill in what the kernels give a sequence of
+    length 0: score = -inf, logZ = loglik = NaN."""
+    return torch.full((B,), value, dtype=torch.float32, device=device)
+
+
 def viterbi(log_pi, log_A, em, lengths=None):
     """MAP state path under the Prior's tables.
 
@@ -129,6 +136,8 @@ def viterbi(log_pi, log_A, em, lengths=None):
     length), score (B,) fp32.  Bit-exact vs the fp32 oracle contract.
     """
     log_pi, log_A, em, lengths, B, T, K = _hmm_inputs(log_pi, log_A, em, lengths)
+    if T == 0:
+        return torch.empty((B, 0), dtype=torch.int32, device=em.device), _length0(B, float("-inf"), em.device)
     path = torch.empty((B, T), dtype=torch.int32, device=em.device)
     score = torch.empty((B,), dtype=torch.float32, device=em.device)
     lib = _ext.load()
@@ -143,6 +152,8 @@ def viterbi(log_pi, log_A, em, lengths=None):
 def _forward_backward_plain(log_pi, log_A, em, lengths=None):
     """gamma and logZ as plain tensors (vqhmm_fwdbwd_f32, any supported K)."""
     log_pi, log_A, em, lengths, B, T, K = _hmm_inputs(log_pi, log_A, em, lengths)
+    if T == 0:
+        return torch.empty((B, 0, K), dtype=torch.float32, device=em.device), _length0(B, float("nan"), em.device)
     gamma = torch.empty((B, T, K), dtype=torch.float32, device=em.device)
     logZ = torch.empty((B,), dtype=torch.float32, device=em.device)
     lib = _ext.load()
@@ -159,6 +170,9 @@ PAIR_MAX_K = 32  # the filter / xi kernels' state limit (hmm_pair.hip)
 
 def _fwdbwd_xi(log_pi, log_A, em, lengths, B, T, K):
     """vqhmm_fwdbwd_xi_f32 on prepared inputs -> (gamma, xi, logZ)."""
+    if T == 0:
+        return (torch.empty((B, 0, K), dtype=torch.float32, device=em.device),
+                torch.empty((B, 0, K, K), dtype=torch.float32, device=em.device), _length0(B, float("nan"), em.device))
     gamma = torch.empty((B, T, K), dtype=torch.float32, device=em.device)
     xi = torch.empty((B, T, K, K), dtype=torch.float32, device=em.device)
     logZ = torch.empty((B,), dtype=torch.float32, device=em.device)
@@ -222,6 +236,10 @@ def forward_filter(log_pi, log_A, em, lengths=None):
     the length, 0 past it), and loglik (B,) = log p(x_{1:L}) (NaN for length 0).  Unlike gamma,
     filt[b,t] does not look at steps after t.  1 <= K <= 32."""
     log_pi, log_A, em, lengths, B, T, K = _hmm_inputs(log_pi, log_A, em, lengths)
+    if T == 0:
+        if K > PAIR_MAX_K:
+            raise RuntimeError(f"vqhmm: forward_filter (K = {K}, limit {PAIR_MAX_K}) failed: unsupported shape")
+        return torch.empty((B, 0, K), dtype=torch.float32, device=em.device), _length0(B, float("nan"), em.device)
     filt = torch.empty((B, T, K), dtype=torch.float32, device=em.device)
     loglik = torch.empty((B,), dtype=torch.float32, device=em.device)
     with torch.no_grad():
